@@ -11,7 +11,10 @@ batch of 32 per domain -- SURVEY 8d M1: "at 1/2/4/8 GPUs, global bs 32 (4/GPU at
   second over all ranks (a step consumes ``bs`` samples from each of the three domains; the raw-image
   figure is 3x and reported next to it); ``scaling`` is "strong": the job's work per step does not change with N.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
+
+``--dump-outputs DIR`` writes what the last timed headline step computed (``dump_outputs``) as DIR/<name>.npy; the step's
+random draws are seeded, so two builds run with the same arguments can be compared output for output.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -36,6 +39,7 @@ The JSON line also carries
 import argparse
 import json
 import os
+import random
 import sys
 import time
 from pathlib import Path
@@ -1010,6 +1014,47 @@ def infer_block(steps, warmup, rank, world, device, dist, barrier, table_path=""
 SUB_BLOCK_TIMEOUT_S = 1200    # watchdog of the sub-blocks (the headline line is complete before they start)
 
 
+DUMP_SAMPLE = 4 * 2 ** 20      # elements of the state sample per model (16 MB of float32 each)
+
+
+def _state_sample(module, n, seed):
+    """A fixed sample of ``module``'s floating-point state (parameters and buffers, state_dict order, flattened end to
+    end): all of it when it holds at most ``n`` elements, else the elements at ``n`` seeded positions (sorted, unique)."""
+    import numpy as np
+
+    items = [v for v in module.state_dict().values() if v.is_floating_point()]
+    sizes = np.array([v.numel() for v in items], dtype=np.int64)
+    total = int(sizes.sum())
+    if total <= n:
+        return np.concatenate([v.detach().float().reshape(-1).cpu().numpy() for v in items])
+    idx = np.unique(np.random.default_rng(seed).integers(0, total, n, dtype=np.int64))
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    parts = []
+    for i, v in enumerate(items):
+        lo, hi = np.searchsorted(idx, [starts[i], starts[i + 1]])
+        if hi > lo:
+            sel = torch.from_numpy(idx[lo:hi] - starts[i]).to(v.device)
+            parts.append(v.detach().reshape(-1).index_select(0, sel).float().cpu().numpy())
+    return np.concatenate(parts)
+
+
+def dump_outputs(out_dir, T, step_out):
+    """What the last timed ``Trainer.train_step`` handed back and left behind: its (g_loss, d_loss), every term of its
+    ``loss_log`` (float64 scalars) and a seeded sample of the updated G and D state (float32, < 64 MB in all)."""
+    import numpy as np
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    g, d = step_out
+    np.save(out / "g_loss.npy", np.asarray(float(g), dtype=np.float64))
+    np.save(out / "d_loss.npy", np.asarray(float(d), dtype=np.float64))
+    for k, v in sorted(T.loss_log.items()):
+        np.save(out / ("loss_log.%s.npy" % k), np.asarray(float(v), dtype=np.float64))
+    for name, mod, seed in (("G", T.G, 0), ("D", T.D, 1)):
+        np.save(out / ("%s_state_sample.npy" % name), _state_sample(mod, DUMP_SAMPLE, seed).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1037,7 +1082,14 @@ def main():
                          "development run and the line says so")
     ap.add_argument("--only", default="", help="run ONE workload as the only measurement (profiling aid): "
                                                "painter | masker | slice | infer | infer32")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed headline step computed to DIR/<name>.npy "
+                         "(losses, and a fixed seeded sample of the updated G and D state) for output-for-output comparison")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.only:
+        ap.error("--dump-outputs writes the headline step's outputs; it does not combine with --only")
 
     # multi-GPU knobs reach the reducer / RCCL through the environment (read at communicator / reducer construction)
     if args.ddp_bucket_mb > 0:
@@ -1071,6 +1123,9 @@ def main():
         else:
             dist.init_process_group(backend)
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
+    # the same inputs from run to run: the step's own random draws (the Painter's latent z, GANLoss's label flip) are seeded
+    random.seed(rank)
+    torch.manual_seed(rank)
 
     def barrier():
         if dist is not None:
@@ -1119,12 +1174,14 @@ def main():
     # first bracketed step, that was 84 device mallocs inside the timed region (``allocator`` in the line reports the count).
     serial_warm = {"on": not args.no_launch_events}
 
+    last = {}
+
     def step():
         bracket = count["i"] % EVENT_EVERY == 0 and (timer.armed or serial_warm["on"])
         timer.enabled = timer.armed and bracket
         T.overlap_branches = overlap_default and not bracket
         count["i"] += 1
-        T.train_step(batch)
+        last["out"] = T.train_step(batch)
 
     timer.armed = False
     for _ in range(args.warmup):
@@ -1144,6 +1201,8 @@ def main():
     timer.armed = timer.enabled = False
     uninstall()
     elapsed = max_over_ranks(elapsed, dist, device)
+    if args.dump_outputs and rank == 0:       # before the extra steps below move the weights on
+        dump_outputs(args.dump_outputs, T, last["out"])
     # every MFMA kernel of the step against both rooflines: EXTRA single-stream steps after the timed region (rank 0 of a
     # single-GPU run only: under torchrun an un-reduced extra step would leave the ranks' buckets out of step)
     all_timer = None

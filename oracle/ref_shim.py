@@ -1,9 +1,8 @@
 """TEST INFRASTRUCTURE (container-only): import the read-only reference at /root/reference.
 
-This module is used ONLY by ``oracle/make_golden.py`` (to generate the committed fixtures under
-``tests/golden/``) and by ``tests/test_oracle_vs_reference.py`` (skipped when /root/reference is absent,
-i.e. on the GPU box).  Nothing in the product path (``climategan_amd/``), in ``bench.py`` or in
-``__graft_entry__.smoke()`` imports it: the reference never travels.
+This module is used ONLY by the ``oracle/make_golden*.py`` generators (to write the committed fixtures under
+``tests/golden/``) and by the measurement scripts under ``tests/devtools/``.  No test, nothing in the product path
+(``climategan_amd/``), ``bench.py`` or ``__graft_entry__.smoke()`` imports it: the reference never travels.
 
 Recipe:
   * the reference's ``climategan/__init__.py:4-8`` imports every submodule (and thus comet_ml, kornia,

@@ -1,13 +1,15 @@
 """How far is the fp32 CPU evaluation of the eval-mode Masker from float64 on the infer_640 fixture?  (the noise floor any
 fp32-grade implementation sits at when compared with the reference's fp32 golden)"""
 import sys, time
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+from pathlib import Path
+ROOT = Path(__file__).resolve().parents[2]
+sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / 'tests'))
 import numpy as np, torch
 from oracle import cpu_ref
 from oracle.make_golden_640 import CASES_640, generator_fill, infer_inputs
 import json
 case = CASES_640["infer_640"]
-shapes = {k: tuple(v) for k, v in json.load(open('/root/repo/tests/golden/generator_masker_shapes.json')).items()}
+shapes = {k: tuple(v) for k, v in json.load(open(ROOT / 'tests' / 'golden' / 'generator_masker_shapes.json')).items()}
 sd = {k: torch.from_numpy(v) for k, v in generator_fill(shapes, case).items()}
 x = torch.from_numpy(infer_inputs(case)["x"])[:1]
 torch.set_num_threads(8)

@@ -1,5 +1,7 @@
 import sys, collections
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+from pathlib import Path
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / 'tests'))
 import torch, bench
 from test_gpu_determinism import _run_steps
 dev = torch.device("cuda:0")

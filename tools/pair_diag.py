@@ -1,5 +1,7 @@
 import sys, random
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+from pathlib import Path
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / 'tests'))
 import numpy as np, torch
 from helpers import load_golden, t
 from oracle.make_golden_640 import CASES_640, generator_fill, infer_inputs
