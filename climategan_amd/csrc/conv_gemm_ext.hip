@@ -506,7 +506,7 @@ int conv_gemm_splitk_launch(const ConvGemmArgs& a, int ksplit, float* ws, int dt
   return CGAN_OK;
 }
 
-// ``a`` describes the data gradient as conv_mfma.hip's dgrad_params leaves it: x = dy (h_in x w_in = its stored extent),
+// ``a`` describes the data gradient as conv_mfma.hip's plan_dgrad leaves it: x = dy (h_in x w_in = its stored extent),
 // h_out x w_out = the forward input's extent, kh / kw = the forward kernel; cls[] filled by the caller per class
 int conv_gemm_cls_launch(const ConvGemmArgs& a, int cls_s, const ConvGemmCls* cls, int dtype, hipStream_t s) {
   ConvGemmExtArgs q;

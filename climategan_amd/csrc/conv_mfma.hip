@@ -633,8 +633,7 @@ int fill_params(ConvParams& p, const CganConvDesc* d) {
   p.kgroups = d->kh * d->kw * p.cg; p.ksteps = ceil_div(p.kgroups, 4);
   p.in_ups = d->in_upsample; p.act = d->act; p.slope = d->act_slope; p.in_zs = 1; p.cls_s = 0; p.cls_pad = 0;
   p.has_res = d->has_residual; p.res_ups = d->residual_upsample;
-  p.stats = nullptr;
-  p.res2 = nullptr;
+  p.x = nullptr; p.w = nullptr; p.bias = nullptr; p.res = nullptr; p.res2 = nullptr; p.y = nullptr; p.stats = nullptr;
   p.pair = 0;
   return CGAN_OK;
 }
@@ -692,6 +691,8 @@ CGAN_DEV_ONLY(extern "C" void cgan_debug_set_conv_kernel(int v) { g_conv_force =
 // 1: strided data gradients read dy through zero insertion (the first implementation) instead of by parity classes
 CGAN_KNOB(int, g_dgrad_zero_insert, 0);
 CGAN_DEV_ONLY(extern "C" void cgan_debug_set_dgrad_zero_insert(int v) { g_dgrad_zero_insert = v; })
+CGAN_KNOB(int, g_pair_big, 1);      // dev: 0 = never the 256 x 256 tile for split convs (same-box A/B, kernel-variant tests)
+CGAN_DEV_ONLY(extern "C" void cgan_debug_set_pair_big(int v) { g_pair_big = v; })
 
 extern "C" size_t cgan_conv2d_packed_weight_bytes(const CganConvDesc* d) {
   ConvParams p;
@@ -797,199 +798,6 @@ extern "C" int cgan_conv2d_bind_workspace(void* stream, void* workspace, size_t 
   return CGAN_OK;
 }
 
-static ConvGemmArgs gemm_args(const ConvParams& p) {
-  ConvGemmArgs a;
-  a.x = p.x; a.w = p.w; a.bias = p.bias; a.res = p.res; a.res2 = p.res2; a.y = p.y;
-  a.n = p.n; a.h_in = p.h_in; a.w_in = p.w_in; a.cin_s = p.cin_s;
-  a.cout = p.cout; a.cout_s = p.cout_s; a.ctiles = p.ctiles; a.ksteps = p.ksteps;
-  a.kh = p.kh; a.kw = p.kw; a.stride = p.stride; a.pad = p.pad; a.dil = p.dil; a.pad_mode = p.pad_mode;
-  a.h_out = p.h_out; a.w_out = p.w_out; a.npix = p.npix;
-  a.act = p.act; a.has_res = p.has_res; a.res_ups = p.res_ups; a.slope = p.slope;
-  a.stats = p.stats;
-  return a;
-}
-
-// K slices if this launch (which the size thresholds keep off the plain wide-layer kernel) runs as a split-K launch of the
-// LDS-tiled GEMM with ``ws_bytes`` of workspace; 1 = it does not
-static int splitk_for(const ConvParams& p, size_t ws_bytes) {
-  if (g_conv_force != 0 || p.in_zs != 1 || p.in_ups || p.cls_s || p.pair || p.stats || p.pad < 0) return 1;
-  if (p.cin_p != p.cin_s) return 1;      // (3x3 layers whose per-tap channel extent is padded to 32: cin_s % 32 != 0 anyway)
-  const ConvGemmArgs a = gemm_args(p);
-  const int ks = conv_gemm_splitk_plan(a);
-  if (ks <= 1 || conv_gemm_splitk_workspace_bytes(a, ks) > ws_bytes) return 1;
-  return ks;
-}
-
-// launches the selection below leaves on the general kernel, or on the spatially tiled 3x3 kernel only because the wide-layer
-// kernel's size thresholds refused them (>= 256 input channels: the tiled kernel is not the preferred one there)
-static bool splitk_candidate(int kind, const ConvParams& p) {
-  return kind == CGAN_CONV_KERNEL_GENERAL || (kind == CGAN_CONV_KERNEL_LDS3X3 && p.cin_s >= 256);
-}
-
-// kernel selection shared by the forward and the stride-1 data-gradient entry points
-static int select_conv_kernel(const ConvParams& p, const CganConvDesc* d) {
-  // narrow 3x3 / stride-1 layers (< 256 channels in) are faster in the spatially tiled 3x3 kernel (halo reuse in LDS)
-  const bool prefer_3x3 = conv3x3_lds_applicable(d) && p.cin_s < 256 && g_conv_force != 3;
-  if ((g_conv_force == 0 || g_conv_force == 3) && p.in_zs == 1 && !prefer_3x3 && conv_gemm_applicable(d)) return CGAN_CONV_KERNEL_GEMM;
-  if (g_conv_force != 1 && p.in_zs == 1 && conv3x3_lds_applicable(d)) return CGAN_CONV_KERNEL_LDS3X3;
-  // first-layer convs (8 storage channels in, k != 3): the halo-tiled kernel of the same family (conv_smallcin_kernel)
-  if (g_conv_force == 0 && p.in_zs == 1 && !p.pair && conv_smallcin_applicable(d)) return CGAN_CONV_KERNEL_LDS3X3;
-  return CGAN_CONV_KERNEL_GENERAL;
-}
-
-static int dispatch_conv(ConvParams& p, const CganConvDesc* d, hipStream_t s, const char* what) {
-  const int kind = select_conv_kernel(p, d);
-  if (kind == CGAN_CONV_KERNEL_GEMM) {
-    const ConvGemmArgs a = gemm_args(p);
-    int rc2 = conv_gemm_launch(a, d->dtype, s);
-    if (rc2 != CGAN_OK) return rc2;
-    CGAN_CHECK_LAUNCH(what);
-    return CGAN_OK;
-  }
-  if (splitk_candidate(kind, p)) {
-    // few output pixels, long K: K slices of the LDS-tiled GEMM + an ordered reduce (conv_gemm_ext.hip)
-    const WsSlot slot = ws_lookup((void*)s);
-    const int ks = splitk_for(p, slot.bytes);
-    if (ks > 1) {
-      int rc2 = conv_gemm_splitk_launch(gemm_args(p), ks, (float*)slot.ws, d->dtype, s);
-      if (rc2 != CGAN_OK) return rc2;
-      CGAN_CHECK_LAUNCH(what);
-      return CGAN_OK;
-    }
-  }
-  if (kind == CGAN_CONV_KERNEL_LDS3X3 && !conv3x3_lds_applicable(d)) {        // the first-layer kernel
-    Conv3x3LdsArgs a;
-    a.x = p.x; a.w = p.w; a.bias = p.bias; a.res = p.res; a.y = p.y;
-    a.n = p.n; a.h = p.h_out; a.w_ = p.w_out; a.hi = p.h_in; a.wi = p.w_in; a.pad = p.pad; a.reflect = 0;
-    a.shuffle = 0; a.shuffle_w = 0; a.k = p.kh; a.stride = p.stride;
-    a.hx = p.hx; a.wx = p.wx; a.cin = d->c_in; a.cin_s = p.cin_s; a.cin_p = p.cin_p;
-    a.cout = p.cout; a.cout_s = p.cout_s; a.ctiles = p.ctiles; a.ksteps = p.ksteps;
-    a.in_ups = 0; a.act = p.act; a.has_res = 0; a.res_ups = 0; a.slope = p.slope;
-    int rc2 = conv_smallcin_launch(a, d->dtype, s);
-    if (rc2 != CGAN_OK) return rc2;
-    CGAN_CHECK_LAUNCH(what);
-    return CGAN_OK;
-  }
-  if (kind == CGAN_CONV_KERNEL_LDS3X3) {
-    Conv3x3LdsArgs a;
-    a.x = p.x; a.w = p.w; a.bias = p.bias; a.res = p.res; a.y = p.y;
-    a.n = p.n; a.h = p.h_out; a.w_ = p.w_out; a.hi = p.h_in; a.wi = p.w_in; a.pad = p.pad;
-    a.reflect = p.pad_mode == CGAN_PAD_REFLECT;
-    a.shuffle = 0; a.shuffle_w = 0; a.k = 0; a.stride = 0;
-    a.hx = p.hx; a.wx = p.wx; a.cin = d->c_in; a.cin_s = p.cin_s; a.cin_p = p.cin_p;
-    a.cout = p.cout; a.cout_s = p.cout_s; a.ctiles = p.ctiles; a.ksteps = p.ksteps;
-    a.in_ups = p.in_ups; a.act = p.act; a.has_res = p.has_res; a.res_ups = p.res_ups; a.slope = p.slope;
-    int rc2 = conv3x3_lds_launch(a, d->dtype, s);
-    if (rc2 != CGAN_OK) return rc2;
-    CGAN_CHECK_LAUNCH(what);
-    return CGAN_OK;
-  }
-  if (d->dtype == CGAN_F16) launch<F16>(p, s);
-  else launch<BF16>(p, s);
-  CGAN_CHECK_LAUNCH(what);
-  return CGAN_OK;
-}
-
-extern "C" int cgan_conv2d_nhwc_fwd(const void* x, const void* packed_w, const float* bias_padded, const void* residual,
-                                    void* y, const CganConvDesc* d, void* stream) {
-  ConvParams p;
-  int rc = fill_params(p, d);
-  if (rc != CGAN_OK) return rc;
-  CGAN_REQUIRE(x && packed_w && y, "conv2d_nhwc_fwd: null pointer");
-  CGAN_REQUIRE(!d->has_bias || bias_padded, "conv2d_nhwc_fwd: has_bias but bias is null");
-  CGAN_REQUIRE(!d->has_residual || residual, "conv2d_nhwc_fwd: has_residual but residual is null");
-  p.x = (const uint16_t*)x; p.w = (const u32x4*)packed_w; p.bias = d->has_bias ? bias_padded : nullptr;
-  p.res = (const uint16_t*)residual; p.y = (uint16_t*)y;
-  return dispatch_conv(p, d, (hipStream_t)stream, "conv2d_nhwc_fwd");
-}
-
-// Split-precision forward (round 4): see the header.  The general gather kernel, or (round 5) the LDS-tiled GEMM for wide layers.
-CGAN_KNOB(int, g_pair_big, 1);      // dev: 0 = never the 256 x 256 tile for split convs (same-box A/B, kernel-variant tests)
-CGAN_DEV_ONLY(extern "C" void cgan_debug_set_pair_big(int v) { g_pair_big = v; })
-extern "C" int cgan_conv2d_nhwc_fwd_pair(const void* x3, const void* packed_w3, const float* bias_padded,
-                                         const void* residual3, void* y3, const CganConvDesc* d, void* stream) {
-  ConvParams p;
-  int rc = fill_params(p, d);
-  if (rc != CGAN_OK) return rc;
-  CGAN_REQUIRE(x3 && packed_w3 && y3, "conv2d_nhwc_fwd_pair: null pointer");
-  CGAN_REQUIRE(!d->has_bias || bias_padded, "conv2d_nhwc_fwd_pair: has_bias but bias is null");
-  CGAN_REQUIRE(!d->has_residual || residual3, "conv2d_nhwc_fwd_pair: has_residual but residual is null");
-  const int nb = cgan_split_blocks(d->dtype);
-  CGAN_REQUIRE((d->c_in % (8 * nb)) == 0, "conv2d_nhwc_fwd_pair: c_in must be the %d * round_up(C, 8) storage channels of a split map", nb);
-  CGAN_REQUIRE((double)p.npix * p.cout_s * cgan_split_store_blocks(d->dtype) * 2.0 < 4294967295.0, "conv2d_nhwc_fwd_pair: output map of 4 GiB or more");
-  p.x = (const uint16_t*)x3; p.w = (const u32x4*)packed_w3; p.bias = d->has_bias ? bias_padded : nullptr;
-  p.res = (const uint16_t*)residual3; p.y = (uint16_t*)y3;
-  p.pair = 1;
-  p.csb = p.cin_s / nb;                                   // the input map stores each component once: NS blocks of csb
-  p.xs = cgan_split_store_blocks(d->dtype) * p.csb;
-  hipStream_t s = (hipStream_t)stream;
-  // wide layers on the LDS-tiled GEMM (round 5): whole 32-channel k-steps per tap, zero padding, no folded upsample, enough
-  // pixels for its 128 / 256-pixel block tiles; everything else stays on the gather kernel
-  if (g_conv_force == 0 && p.in_zs == 1 && !p.in_ups && p.cin_p == p.cin_s && p.pad >= 0 && p.npix >= 1024 && p.ksteps >= 4) {
-    const ConvGemmArgs a = gemm_args(p);
-    // >= 192 couts and whole 64-channel K stages: the 256 x 256 / eight-wave tile (round 6: 0.30 -> 0.4+ of MFMA on the
-    // ResNet layer3 / layer4 / ASPP convs, which are most of a split-precision Masker)
-    if (g_pair_big && conv_gemm_big_pair_ok(a, d->dtype)) {
-      rc = conv_gemm_big_pair_launch(a, d->dtype, s);
-      if (rc != CGAN_OK) return rc;
-      CGAN_CHECK_LAUNCH("conv2d_nhwc_fwd_pair(gemm 256)");
-      return CGAN_OK;
-    }
-    if (conv_gemm_ext_shape_ok(a) && (double)p.npix * p.cout_s * cgan_split_store_blocks(d->dtype) < 2147483647.0) {
-      rc = conv_gemm_pair_launch(a, d->dtype, s);
-      if (rc != CGAN_OK) return rc;
-      CGAN_CHECK_LAUNCH("conv2d_nhwc_fwd_pair(gemm)");
-      return CGAN_OK;
-    }
-  }
-  if (d->dtype == CGAN_F16) launch<F16>(p, s);
-  else launch<BF16>(p, s);
-  CGAN_CHECK_LAUNCH("conv2d_nhwc_fwd_pair");
-  return CGAN_OK;
-}
-
-// Forward with training-mode BatchNorm statistics from the kernel's epilogue (round 3): see the header.
-static const float k_bias_sentinel = 0.f;    // never dereferenced
-static int stats_chunk_pixels(ConvParams& p, const CganConvDesc* d) {
-  if (d->has_residual || d->act != CGAN_ACT_NONE || d->in_upsample) return 0;
-  if (select_conv_kernel(p, d) != CGAN_CONV_KERNEL_GEMM) return 0;
-  ConvGemmArgs a;
-  a.x = nullptr; a.w = nullptr; a.bias = d->has_bias ? &k_bias_sentinel : nullptr;   // choose() keys on it: the query must pick what the launch picks
-  a.res = nullptr; a.res2 = nullptr; a.y = nullptr; a.stats = nullptr;
-  a.n = p.n; a.h_in = p.h_in; a.w_in = p.w_in; a.cin_s = p.cin_s;
-  a.cout = p.cout; a.cout_s = p.cout_s; a.ctiles = p.ctiles; a.ksteps = p.ksteps;
-  a.kh = p.kh; a.kw = p.kw; a.stride = p.stride; a.pad = p.pad; a.dil = p.dil; a.pad_mode = p.pad_mode;
-  a.h_out = p.h_out; a.w_out = p.w_out; a.npix = p.npix;
-  a.act = p.act; a.has_res = p.has_res; a.res_ups = p.res_ups; a.slope = p.slope;
-  return conv_gemm_stats_chunk_pixels(a, d->dtype);
-}
-
-extern "C" int32_t cgan_conv2d_stats_chunk_pixels(const CganConvDesc* d) {
-  ConvParams p;
-  if (fill_params(p, d) != CGAN_OK) return 0;
-  return stats_chunk_pixels(p, d);
-}
-
-extern "C" int cgan_conv2d_nhwc_fwd_stats(const void* x, const void* packed_w, const float* bias_padded, void* y,
-                                          float* partial, size_t partial_bytes, const CganConvDesc* d, void* stream) {
-  ConvParams p;
-  int rc = fill_params(p, d);
-  if (rc != CGAN_OK) return rc;
-  CGAN_REQUIRE(x && packed_w && y && partial, "conv2d_nhwc_fwd_stats: null pointer");
-  CGAN_REQUIRE(!d->has_bias || bias_padded, "conv2d_nhwc_fwd_stats: has_bias but bias is null");
-  const int ppb = stats_chunk_pixels(p, d);
-  CGAN_REQUIRE(ppb > 0, "conv2d_nhwc_fwd_stats: this descriptor's kernel writes no statistics "
-                        "(cgan_conv2d_stats_chunk_pixels returned 0)");
-  const size_t need = (size_t)(p.npix / ppb) * p.cout_s * 2 * sizeof(float);
-  if (partial_bytes < need) {
-    cgan_set_error("conv2d_nhwc_fwd_stats: partial buffer %zu B < required %zu B", partial_bytes, need);
-    return CGAN_ERR_WORKSPACE;
-  }
-  p.x = (const uint16_t*)x; p.w = (const u32x4*)packed_w; p.bias = d->has_bias ? bias_padded : nullptr;
-  p.res = nullptr; p.y = (uint16_t*)y; p.stats = partial;
-  return dispatch_conv(p, d, (hipStream_t)stream, "conv2d_nhwc_fwd_stats");
-}
-
 // ------------------------------------------------------------------------------------------------
 // backward-data: dx = conv_transpose(dy, w) expressed as a stride-1 convolution of dy (read through zero insertion
 // when the forward stride is > 1) with the channel-transposed, tap-flipped weights, pad' = dil (k-1) - pad.
@@ -1010,30 +818,6 @@ static int dgrad_desc(const CganConvDesc* f, CganConvDesc* t) {
   CGAN_REQUIRE(t->h_out <= f->h_in && t->w_out <= f->w_in && t->h_out > 0 && t->w_out > 0,
                "conv2d bwd_data: inconsistent forward descriptor");
   t->in_upsample = 0; t->act = CGAN_ACT_NONE; t->has_bias = 0; t->has_residual = 0; t->residual_upsample = 0;
-  return CGAN_OK;
-}
-
-static int dgrad_params(ConvParams& p, const CganConvDesc* f, CganConvDesc* t) {
-  int rc = dgrad_desc(f, t);
-  if (rc != CGAN_OK) return rc;
-  const int pad_t = t->pad;
-  if (pad_t < 0) t->pad = 0;                       // fill_params wants pad >= 0 (only ASPP's padded 1x1 gets here)
-  if (pad_t < 0) { t->h_out = t->h_in; t->w_out = t->w_in; }
-  rc = fill_params(p, t);
-  if (rc != CGAN_OK) return rc;
-  p.pad = pad_t;
-  // rows / columns of the forward input that no output window reached (floor in the output-size formula) still get
-  // written: every tap lands outside the virtual extent there, so they come out zero
-  p.h_out = f->h_in; p.w_out = f->w_in;
-  p.npix = f->n * f->h_in * f->w_in;
-  p.hx = f->h_out; p.wx = f->w_out;                // stored extent of dy
-  p.in_zs = f->stride;
-  if (f->stride > 1 && f->dilation == 1 && pad_t >= 0 && g_dgrad_zero_insert == 0) {
-    // parity classes: coordinates are those of the stored dy, no zero insertion
-    p.cls_s = f->stride; p.cls_pad = pad_t; p.in_zs = 1;
-    p.h_in = p.hx; p.w_in = p.wx;
-  }
-  t->h_out = f->h_in; t->w_out = f->w_in;
   return CGAN_OK;
 }
 
@@ -1084,78 +868,69 @@ __global__ void pack_dgrad_subpixel_kernel(const float* __restrict__ w, const fl
   }
 }
 
-static size_t dgrad_packed_fragments(const ConvParams& p) {
-  if (!p.cls_s) return (size_t)p.ctiles * p.ksteps * 64;
-  size_t ks = 0;
-  for (int c = 0; c < p.cls_s * p.cls_s; ++c) ks += cls_ksteps(p.cls_s, p.kh, p.kw, p.cls_pad, p.cg, c);
-  return (size_t)p.ctiles * ks * 64;
+// ------------------------------------------------------------------------------------------------
+// Launch plan: which kernel runs a descriptor, decided once.  The launches, the kernel-kind query, the statistics-chunk
+// query, the fused-or-not choice of the ReLU data gradient and the data-gradient weight layout are all read off it.
+// ------------------------------------------------------------------------------------------------
+namespace {
+enum ConvRoute {
+  ROUTE_GEMM,        // wide-layer LDS-tiled GEMM (conv_gemm.hip: choose() picks the kernel and tile)
+  ROUTE_SPLITK,      // few output pixels, long K: K slices of the LDS-tiled GEMM + an ordered reduce (conv_gemm_ext.hip)
+  ROUTE_LDS3X3,      // spatially tiled 3x3 (conv3x3_lds.hip)
+  ROUTE_SMALLCIN,    // first-layer convs, 8 storage channels in: the halo-tiled kernel of the same family (conv_smallcin_kernel)
+  ROUTE_SUBPIXEL,    // data gradient of the discriminators' 4x4 / stride-2 input conv on the tiled 3x3 kernel (above)
+  ROUTE_CLS_GEMM,    // strided data gradient by output parity classes on the LDS-tiled GEMM (conv_gemm_ext.hip)
+  ROUTE_PAIR_BIG,    // split-precision forward on the 256 x 256 tile (conv_gemm_big.hip)
+  ROUTE_PAIR_GEMM,   // split-precision forward on the LDS-tiled GEMM (conv_gemm_ext.hip)
+  ROUTE_GENERAL,     // the general gather kernel (this file)
+};
+enum { FWD_PLAIN, FWD_STATS, FWD_PAIR };
+// residual epilogue of a data gradient: dx_add, [relu_out > 0], or both ([relu_out > 0] * (dgrad + dx_add))
+enum { RES_NONE = 0, RES_ADD = 1, RES_RELU = 2, RES_ADD_RELU = 3 };
+
+struct ConvPlan {
+  ConvRoute route;
+  ConvParams p;       // shapes and modes; the entry point binds the pointers
+  CganConvDesc d;     // what the route's kernel computes: the forward descriptor, or the data gradient's stride-1 transform
+  int ksplit;         // ROUTE_SPLITK: K slices ...
+  float* ws;          // ... and the launch stream's workspace
+};
+
+ConvGemmArgs gemm_args(const ConvParams& p) {
+  ConvGemmArgs a;
+  a.x = p.x; a.w = p.w; a.bias = p.bias; a.res = p.res; a.res2 = p.res2; a.y = p.y;
+  a.n = p.n; a.h_in = p.h_in; a.w_in = p.w_in; a.cin_s = p.cin_s;
+  a.cout = p.cout; a.cout_s = p.cout_s; a.ctiles = p.ctiles; a.ksteps = p.ksteps;
+  a.kh = p.kh; a.kw = p.kw; a.stride = p.stride; a.pad = p.pad; a.dil = p.dil; a.pad_mode = p.pad_mode;
+  a.h_out = p.h_out; a.w_out = p.w_out; a.npix = p.npix;
+  a.act = p.act; a.has_res = p.has_res; a.res_ups = p.res_ups; a.slope = p.slope;
+  a.stats = p.stats;
+  return a;
 }
 
-extern "C" size_t cgan_conv2d_dgrad_packed_weight_bytes(const CganConvDesc* fwd) {
-  ConvParams p;
-  CganConvDesc t;
-  if (dgrad_params(p, fwd, &t) != CGAN_OK) return 0;
-  if (dgrad_subpixel(fwd)) return (size_t)9 * (((cgan_cs(fwd->c_out) + 31) & ~31) / 32) * 64 * 16;
-  const size_t fr = dgrad_packed_fragments(p);
-  return (fr ? fr : 64) * 16;
-}
-
-extern "C" int cgan_conv2d_pack_weight_dgrad(const float* w_oihw, const float* sigma, void* packed,
-                                             const CganConvDesc* fwd, void* stream) {
-  ConvParams p;
-  CganConvDesc t;
-  int rc = dgrad_params(p, fwd, &t);
-  if (rc != CGAN_OK) return rc;
-  CGAN_REQUIRE(w_oihw && packed, "conv2d_pack_weight_dgrad: null pointer");
-  if (dgrad_subpixel(fwd)) {
-    const int cin_p = (cgan_cs(fwd->c_out) + 31) & ~31;
-    const int tot = 9 * (cin_p / 32) * 64;
-    hipStream_t st = (hipStream_t)stream;
-    if (fwd->dtype == CGAN_F16)
-      hipLaunchKernelGGL(pack_dgrad_subpixel_kernel<F16>, dim3(ceil_div(tot, 256)), dim3(256), 0, st, w_oihw, sigma,
-                         (uint16_t*)packed, fwd->c_out, fwd->c_in, cin_p);
-    else
-      hipLaunchKernelGGL(pack_dgrad_subpixel_kernel<BF16>, dim3(ceil_div(tot, 256)), dim3(256), 0, st, w_oihw, sigma,
-                         (uint16_t*)packed, fwd->c_out, fwd->c_in, cin_p);
-    CGAN_CHECK_LAUNCH("conv2d_pack_weight_dgrad(sub-pixel)");
-    return CGAN_OK;
+Conv3x3LdsArgs lds_args(const ConvPlan& pl) {
+  const ConvParams& p = pl.p;
+  Conv3x3LdsArgs a;
+  a.x = p.x; a.w = p.w; a.bias = p.bias; a.res = p.res; a.y = p.y;
+  a.n = p.n; a.h = p.h_out; a.w_ = p.w_out; a.hi = p.h_in; a.wi = p.w_in; a.pad = p.pad;
+  a.reflect = p.pad_mode == CGAN_PAD_REFLECT;
+  a.hx = p.hx; a.wx = p.wx; a.cin = pl.d.c_in; a.cin_s = p.cin_s; a.cin_p = p.cin_p;
+  a.cout = p.cout; a.cout_s = p.cout_s; a.ctiles = p.ctiles; a.ksteps = p.ksteps;
+  a.in_ups = p.in_ups; a.act = p.act; a.has_res = p.has_res; a.res_ups = p.res_ups; a.slope = p.slope;
+  a.shuffle = 0; a.shuffle_w = 0; a.k = 0; a.stride = 0;
+  if (pl.route == ROUTE_SMALLCIN) {       // (zero padding, no folded upsample, no residual: conv_smallcin_applicable)
+    a.k = p.kh; a.stride = p.stride; a.res_ups = 0;
+  } else if (pl.route == ROUTE_SUBPIXEL) {
+    // a 3x3 / pad-1 conv over the stored dy (hx x wx) to 16 rows (a, b, c), scattered to the forward input's h_out x w_out
+    a.h = a.hi = p.hx; a.w_ = a.wi = p.wx; a.pad = 1; a.slope = 0.f;
+    a.cout = 16; a.cout_s = 16; a.ctiles = 1; a.ksteps = 9 * (a.cin_p / 32);
+    a.shuffle = p.h_out; a.shuffle_w = p.w_out;
   }
-  if (p.cls_s) {
-    int max_ks = 1;
-    for (int c = 0; c < p.cls_s * p.cls_s; ++c) {
-      const int k = cls_ksteps(p.cls_s, p.kh, p.kw, p.cls_pad, p.cg, c);
-      max_ks = k > max_ks ? k : max_ks;
-    }
-    const int tot = p.ctiles * max_ks * 64;
-    const dim3 grid(ceil_div(tot, 256) < 1024 ? ceil_div(tot, 256) : 1024, p.cls_s * p.cls_s);
-    hipStream_t st = (hipStream_t)stream;
-    if (fwd->dtype == CGAN_F16)
-      hipLaunchKernelGGL(pack_dgrad_classes_kernel<F16>, grid, dim3(256), 0, st, w_oihw, sigma, (uint16_t*)packed, t.c_out,
-                         t.c_in, p.cin_p, t.kh, t.kw, p.ctiles, p.cls_s, p.cls_pad);
-    else
-      hipLaunchKernelGGL(pack_dgrad_classes_kernel<BF16>, grid, dim3(256), 0, st, w_oihw, sigma, (uint16_t*)packed, t.c_out,
-                         t.c_in, p.cin_p, t.kh, t.kw, p.ctiles, p.cls_s, p.cls_pad);
-    CGAN_CHECK_LAUNCH("conv2d_pack_weight_dgrad(classes)");
-    return CGAN_OK;
-  }
-  const int total = p.ctiles * p.ksteps * 64;
-  const int blocks = ceil_div(total, 256) < 2048 ? ceil_div(total, 256) : 2048;
-  hipStream_t s = (hipStream_t)stream;
-  // rows = forward c_in, K channels = forward c_out
-  if (fwd->dtype == CGAN_F16)
-    hipLaunchKernelGGL(pack_conv_weight_kernel<F16>, dim3(blocks), dim3(256), 0, s, w_oihw, (const float*)nullptr, sigma,
-                       (uint16_t*)packed, (float*)nullptr, t.c_out, t.c_in, p.cin_p, t.kh, t.kw, p.ctiles, p.ksteps, 1);
-  else
-    hipLaunchKernelGGL(pack_conv_weight_kernel<BF16>, dim3(blocks), dim3(256), 0, s, w_oihw, (const float*)nullptr, sigma,
-                       (uint16_t*)packed, (float*)nullptr, t.c_out, t.c_in, p.cin_p, t.kh, t.kw, p.ctiles, p.ksteps, 1);
-  CGAN_CHECK_LAUNCH("conv2d_pack_weight_dgrad");
-  return CGAN_OK;
+  return a;
 }
 
-// parity-class data gradient on the LDS-tiled GEMM (conv_gemm_ext.hip): the class table, or false = stays on the general kernel
-static bool cls_on_gemm(const ConvParams& p, ConvGemmCls (&cls)[4]) {
-  if (!p.cls_s || p.cls_s > 2 || g_conv_force != 0 || p.cin_p != p.cin_s || p.pair) return false;
-  if (!conv_gemm_ext_shape_ok(gemm_args(p)) || p.cout_s < 64) return false;
+// the class table of a parity-class data gradient on the LDS-tiled GEMM
+void cls_table(const ConvParams& p, ConvGemmCls (&cls)[4]) {
   int koff = 0;
   for (int c = 0; c < p.cls_s * p.cls_s; ++c) {
     const int ca = c / p.cls_s, cb = c % p.cls_s;
@@ -1167,128 +942,340 @@ static bool cls_on_gemm(const ConvParams& p, ConvGemmCls (&cls)[4]) {
     if (nty * ntx == 0) cls[c].kh = cls[c].kw = 0;
     koff += cls_ksteps(p.cls_s, p.kh, p.kw, p.cls_pad, p.cg, c);
   }
-  return true;
 }
 
-// ws_bytes: the split-K workspace the launch in question would find (a split-K launch needs its stream's binding)
-static int kernel_kind_impl(const CganConvDesc* d, int32_t bwd_data, size_t ws_bytes) {
-  ConvParams p;
-  if (!bwd_data) {
-    int rc = fill_params(p, d);
-    if (rc != CGAN_OK) return rc;
-    const int kind = select_conv_kernel(p, d);
-    return splitk_candidate(kind, p) && splitk_for(p, ws_bytes) > 1 ? CGAN_CONV_KERNEL_GEMM : kind;
+// the stride-1 cascade: forward, statistics forward (no split-K: the statistics come from the GEMM's own epilogue) and the
+// stride-1 'same' data gradient.  ``ws``: the split-K workspace the launch would find.
+ConvRoute route_stride1(ConvPlan& pl, bool stats, const WsSlot& ws) {
+  const ConvParams& p = pl.p;
+  const CganConvDesc* d = &pl.d;
+  const bool lds = conv3x3_lds_applicable(d);
+  // narrow 3x3 / stride-1 layers (< 256 channels in) are faster in the spatially tiled 3x3 kernel (halo reuse in LDS)
+  const bool prefer_3x3 = lds && p.cin_s < 256 && g_conv_force != 3;
+  if ((g_conv_force == 0 || g_conv_force == 3) && !prefer_3x3 && conv_gemm_applicable(d)) return ROUTE_GEMM;
+  ConvRoute r = ROUTE_GENERAL;
+  if (g_conv_force != 1 && lds) r = ROUTE_LDS3X3;
+  else if (g_conv_force == 0 && conv_smallcin_applicable(d)) r = ROUTE_SMALLCIN;
+  // split-K where the above left the general kernel, or the tiled 3x3 kernel only because the wide-layer kernel's size
+  // thresholds refused the layer (>= 256 input channels: the tiled kernel is not the preferred one there)
+  // (3x3 layers whose per-tap channel extent is padded to 32 have cin_s % 32 != 0: no split-K either way)
+  if ((r == ROUTE_GENERAL || (r == ROUTE_LDS3X3 && p.cin_s >= 256)) && g_conv_force == 0 && !stats && !p.in_ups &&
+      p.cin_p == p.cin_s) {
+    const ConvGemmArgs a = gemm_args(p);
+    const int ks = conv_gemm_splitk_plan(a);
+    if (ks > 1 && conv_gemm_splitk_workspace_bytes(a, ks) <= ws.bytes) {
+      pl.ksplit = ks;
+      pl.ws = (float*)ws.ws;
+      return ROUTE_SPLITK;
+    }
   }
-  CganConvDesc t;
-  int rc = dgrad_params(p, d, &t);
+  return r;
+}
+
+int plan_fwd(ConvPlan& pl, const CganConvDesc* d, int mode, const WsSlot& ws) {
+  ConvParams& p = pl.p;
+  int rc = fill_params(p, d);
   if (rc != CGAN_OK) return rc;
-  const bool plain = d->stride == 1 && p.pad >= 0 && t.h_in + 2 * p.pad - t.dilation * (t.kh - 1) == t.h_out &&
-                     t.w_in + 2 * p.pad - t.dilation * (t.kw - 1) == t.w_out;
-  if (!plain) {
-    if (dgrad_subpixel(d)) return CGAN_CONV_KERNEL_LDS3X3;
-    ConvGemmCls cls[4];
-    return cls_on_gemm(p, cls) ? CGAN_CONV_KERNEL_GEMM : CGAN_CONV_KERNEL_GENERAL;
+  pl.d = *d; pl.ksplit = 1; pl.ws = nullptr;
+  if (mode != FWD_PAIR) {
+    pl.route = route_stride1(pl, mode == FWD_STATS, ws);
+    return CGAN_OK;
   }
-  t.pad = p.pad;
-  const int kind = select_conv_kernel(p, &t);
-  return splitk_candidate(kind, p) && splitk_for(p, ws_bytes) > 1 ? CGAN_CONV_KERNEL_GEMM : kind;
+  // split-precision forward (round 4): see the header
+  const int nb = cgan_split_blocks(d->dtype), ns = cgan_split_store_blocks(d->dtype);
+  CGAN_REQUIRE((d->c_in % (8 * nb)) == 0, "conv2d_nhwc_fwd_pair: c_in must be the %d * round_up(C, 8) storage channels of a split map", nb);
+  CGAN_REQUIRE((double)p.npix * p.cout_s * ns * 2.0 < 4294967295.0, "conv2d_nhwc_fwd_pair: output map of 4 GiB or more");
+  p.pair = 1;
+  p.csb = p.cin_s / nb;                                   // the input map stores each component once: NS blocks of csb
+  p.xs = ns * p.csb;
+  pl.route = ROUTE_GENERAL;
+  // wide layers on the LDS-tiled GEMM (round 5): whole 32-channel k-steps per tap, zero padding, no folded upsample, enough
+  // pixels for its 128 / 256-pixel block tiles; everything else stays on the gather kernel
+  if (g_conv_force == 0 && !p.in_ups && p.cin_p == p.cin_s && p.npix >= 1024 && p.ksteps >= 4) {
+    const ConvGemmArgs a = gemm_args(p);
+    // >= 192 couts and whole 64-channel K stages: the 256 x 256 / eight-wave tile (round 6: 0.30 -> 0.4+ of MFMA on the
+    // ResNet layer3 / layer4 / ASPP convs, which are most of a split-precision Masker)
+    if (g_pair_big && conv_gemm_big_pair_ok(a, d->dtype)) pl.route = ROUTE_PAIR_BIG;
+    else if (conv_gemm_ext_shape_ok(a) && (double)p.npix * p.cout_s * ns < 2147483647.0) pl.route = ROUTE_PAIR_GEMM;
+  }
+  return CGAN_OK;
 }
 
-// the kernel a launch of this descriptor on ``stream`` (of the current device) runs: that stream's workspace decides split-K
-extern "C" int cgan_conv2d_kernel_kind_on(const CganConvDesc* d, int32_t bwd_data, void* stream) {
-  return kernel_kind_impl(d, bwd_data, ws_lookup(stream).bytes);
-}
-// (kept for callers without a stream at hand: answers for the largest workspace bound on the current device)
-extern "C" int cgan_conv2d_kernel_kind(const CganConvDesc* d, int32_t bwd_data) {
-  return kernel_kind_impl(d, bwd_data, ws_max_bytes());
-}
-
-static int bwd_data_impl(const void* dy, const void* packed_w_dgrad, const void* dx_add, void* dx, const CganConvDesc* fwd,
-                         void* stream, int res_mode = 1, const void* relu_out2 = nullptr) {
-  ConvParams p;
-  CganConvDesc t;
-  int rc = dgrad_params(p, fwd, &t);
+// ``f``: the FORWARD descriptor.  RES_ADD_RELU plans the fused launch (has_res = 3) where the GEMM kernel's store path takes
+// it; elsewhere it leaves has_res = 1 and the caller applies the ReLU derivative in a pass of its own.
+int plan_dgrad(ConvPlan& pl, const CganConvDesc* f, int res_mode, const WsSlot& ws) {
+  ConvParams& p = pl.p;
+  CganConvDesc& t = pl.d;
+  int rc = dgrad_desc(f, &t);
   if (rc != CGAN_OK) return rc;
-  CGAN_REQUIRE(dy && packed_w_dgrad && dx, "conv2d_nhwc_bwd_data: null pointer");
-  p.x = (const uint16_t*)dy; p.w = (const u32x4*)packed_w_dgrad; p.bias = nullptr; p.res = nullptr; p.y = (uint16_t*)dx;
-  hipStream_t s = (hipStream_t)stream;
-  const bool plain = fwd->stride == 1 && p.pad >= 0 && t.h_in + 2 * p.pad - t.dilation * (t.kh - 1) == t.h_out &&
-                     t.w_in + 2 * p.pad - t.dilation * (t.kw - 1) == t.w_out;
-  CGAN_REQUIRE(dx_add == nullptr || plain, "conv2d_nhwc_bwd_data_add: only for stride-1 'same' convolutions");
-  if (dx_add) {             // the other gradient contribution of the same tensor rides in the epilogue's residual slot
-    p.res = (const uint16_t*)dx_add;
-    p.has_res = res_mode;         // 1: add the other contribution; 2: the ReLU derivative from the activation's output;
-    p.res2 = (const uint16_t*)relu_out2;   // 3: both (the caller checked conv_gemm_res2_ok)
+  const int pad_t = t.pad;
+  if (pad_t < 0) {                                 // fill_params wants pad >= 0 (only ASPP's padded 1x1 gets here)
+    t.pad = 0;
+    t.h_out = t.h_in; t.w_out = t.w_in;
+  }
+  rc = fill_params(p, &t);
+  if (rc != CGAN_OK) return rc;
+  pl.ksplit = 1; pl.ws = nullptr;
+  t.pad = p.pad = pad_t;
+  // rows / columns of the forward input that no output window reached (floor in the output-size formula) still get
+  // written: every tap lands outside the virtual extent there, so they come out zero
+  t.h_out = p.h_out = f->h_in; t.w_out = p.w_out = f->w_in;
+  p.npix = f->n * f->h_in * f->w_in;
+  p.hx = f->h_out; p.wx = f->w_out;                // stored extent of dy
+  p.in_zs = f->stride;
+  if (f->stride > 1 && f->dilation == 1 && pad_t >= 0 && g_dgrad_zero_insert == 0) {
+    // parity classes: coordinates are those of the stored dy, no zero insertion
+    p.cls_s = f->stride; p.cls_pad = pad_t; p.in_zs = 1;
+    p.h_in = p.hx; p.w_in = p.wx;
+  }
+  // stride 1, output exactly the forward input: an ordinary stride-1 convolution of dy (the forward cascade, residual epilogues)
+  const bool plain = f->stride == 1 && pad_t >= 0 && t.h_in + 2 * pad_t - t.dilation * (t.kh - 1) == t.h_out &&
+                     t.w_in + 2 * pad_t - t.dilation * (t.kw - 1) == t.w_out;
+  if (res_mode != RES_NONE) {     // the other contribution / the ReLU output rides in the epilogue's residual slot
+    CGAN_REQUIRE(plain, "conv2d_nhwc_bwd_data_add / _relu: only for stride-1 'same' convolutions");
+    p.has_res = res_mode == RES_ADD_RELU ? RES_ADD : res_mode;
     p.res_ups = 0;
     t.has_residual = 1;
   }
   if (plain) {
-    t.pad = p.pad;
-    return dispatch_conv(p, &t, s, "conv2d_nhwc_bwd_data");
+    pl.route = route_stride1(pl, false, ws);
+    if (res_mode == RES_ADD_RELU && pl.route == ROUTE_GEMM && conv_gemm_res2_ok(gemm_args(p), t.dtype)) p.has_res = 3;
+  } else if (dgrad_subpixel(f)) {
+    pl.route = ROUTE_SUBPIXEL;
+  } else if (p.cls_s && p.cls_s <= 2 && g_conv_force == 0 && p.cin_p == p.cin_s && conv_gemm_ext_shape_ok(gemm_args(p)) &&
+             p.cout_s >= 64) {
+    pl.route = ROUTE_CLS_GEMM;
+  } else {
+    pl.route = ROUTE_GENERAL;
   }
-  if (dgrad_subpixel(fwd)) {
-    Conv3x3LdsArgs a;
-    a.x = p.x; a.w = p.w; a.bias = nullptr; a.res = nullptr; a.y = p.y;
-    a.n = fwd->n; a.h = fwd->h_out; a.w_ = fwd->w_out; a.hi = fwd->h_out; a.wi = fwd->w_out; a.pad = 1; a.reflect = 0;
-    a.hx = fwd->h_out; a.wx = fwd->w_out;
-    a.cin = fwd->c_out; a.cin_s = cgan_cs(fwd->c_out); a.cin_p = (a.cin_s + 31) & ~31;
-    a.cout = 16; a.cout_s = 16; a.ctiles = 1; a.ksteps = 9 * (a.cin_p / 32);
-    a.in_ups = 0; a.act = CGAN_ACT_NONE; a.has_res = 0; a.res_ups = 0; a.slope = 0.f;
-    a.shuffle = fwd->h_in; a.shuffle_w = fwd->w_in; a.k = 0; a.stride = 0;
-    int rc2 = conv3x3_lds_launch(a, fwd->dtype, s);
-    if (rc2 != CGAN_OK) return rc2;
-    CGAN_CHECK_LAUNCH("conv2d_nhwc_bwd_data(sub-pixel)");
-    return CGAN_OK;
-  }
-  ConvGemmCls cls[4];
-  if (cls_on_gemm(p, cls)) {
-    int rc2 = conv_gemm_cls_launch(gemm_args(p), p.cls_s, cls, fwd->dtype, s);
-    if (rc2 != CGAN_OK) return rc2;
-    CGAN_CHECK_LAUNCH("conv2d_nhwc_bwd_data");
-    return CGAN_OK;
-  }
-  if (fwd->dtype == CGAN_F16) launch<F16>(p, s);
-  else launch<BF16>(p, s);
-  CGAN_CHECK_LAUNCH("conv2d_nhwc_bwd_data");
   return CGAN_OK;
+}
+
+int route_family(ConvRoute r) {
+  switch (r) {
+    case ROUTE_GENERAL: return CGAN_CONV_KERNEL_GENERAL;
+    case ROUTE_LDS3X3: case ROUTE_SMALLCIN: case ROUTE_SUBPIXEL: return CGAN_CONV_KERNEL_LDS3X3;
+    default: return CGAN_CONV_KERNEL_GEMM;
+  }
+}
+
+// pixels per statistics chunk of the plan's kernel, 0 = it writes none.  choose() keys on whether there is a bias, and a
+// query binds no pointers: ``a`` (never a kernel's argument) marks the bias present with a placeholder
+int stats_chunk_pixels(const ConvPlan& pl) {
+  const CganConvDesc& d = pl.d;
+  if (pl.route != ROUTE_GEMM || d.has_residual || d.act != CGAN_ACT_NONE || d.in_upsample) return 0;
+  static const float bias_present = 0.f;
+  ConvGemmArgs a = gemm_args(pl.p);
+  a.bias = d.has_bias ? &bias_present : nullptr;
+  return conv_gemm_stats_chunk_pixels(a, d.dtype);
+}
+
+int launch_plan(const ConvPlan& pl, hipStream_t s, const char* what) {
+  const ConvParams& p = pl.p;
+  const int dt = pl.d.dtype;
+  int rc = CGAN_OK;
+  switch (pl.route) {
+    case ROUTE_GEMM: rc = conv_gemm_launch(gemm_args(p), dt, s); break;
+    case ROUTE_SPLITK: rc = conv_gemm_splitk_launch(gemm_args(p), pl.ksplit, pl.ws, dt, s); break;
+    case ROUTE_LDS3X3: case ROUTE_SUBPIXEL: rc = conv3x3_lds_launch(lds_args(pl), dt, s); break;
+    case ROUTE_SMALLCIN: rc = conv_smallcin_launch(lds_args(pl), dt, s); break;
+    case ROUTE_CLS_GEMM: {
+      ConvGemmCls cls[4];
+      cls_table(p, cls);
+      rc = conv_gemm_cls_launch(gemm_args(p), p.cls_s, cls, dt, s);
+      break;
+    }
+    case ROUTE_PAIR_BIG: rc = conv_gemm_big_pair_launch(gemm_args(p), dt, s); break;
+    case ROUTE_PAIR_GEMM: rc = conv_gemm_pair_launch(gemm_args(p), dt, s); break;
+    case ROUTE_GENERAL:
+      if (dt == CGAN_F16) launch<F16>(p, s);
+      else launch<BF16>(p, s);
+      break;
+  }
+  if (rc != CGAN_OK) return rc;
+  CGAN_CHECK_LAUNCH(what);
+  return CGAN_OK;
+}
+
+void bind(ConvParams& p, const void* x, const void* w, const float* bias, const void* res, void* y) {
+  p.x = (const uint16_t*)x; p.w = (const u32x4*)w; p.bias = bias; p.res = (const uint16_t*)res; p.y = (uint16_t*)y;
+}
+}  // namespace
+
+extern "C" int cgan_conv2d_nhwc_fwd(const void* x, const void* packed_w, const float* bias_padded, const void* residual,
+                                    void* y, const CganConvDesc* d, void* stream) {
+  // (pointers before the plan: an empty output, h_out or w_out = 0, arrives as a null y and is refused here -- the split-K
+  // plan of such a descriptor divides by its zero pixel blocks)
+  CGAN_REQUIRE(x && packed_w && y, "conv2d_nhwc_fwd: null pointer");
+  ConvPlan pl;
+  int rc = plan_fwd(pl, d, FWD_PLAIN, ws_lookup(stream));
+  if (rc != CGAN_OK) return rc;
+  CGAN_REQUIRE(!d->has_bias || bias_padded, "conv2d_nhwc_fwd: has_bias but bias is null");
+  CGAN_REQUIRE(!d->has_residual || residual, "conv2d_nhwc_fwd: has_residual but residual is null");
+  bind(pl.p, x, packed_w, d->has_bias ? bias_padded : nullptr, residual, y);
+  return launch_plan(pl, (hipStream_t)stream, "conv2d_nhwc_fwd");
+}
+
+// Split-precision forward (round 4): see the header.  The general gather kernel, or (round 5) the LDS-tiled GEMM for wide layers.
+extern "C" int cgan_conv2d_nhwc_fwd_pair(const void* x3, const void* packed_w3, const float* bias_padded,
+                                         const void* residual3, void* y3, const CganConvDesc* d, void* stream) {
+  CGAN_REQUIRE(x3 && packed_w3 && y3, "conv2d_nhwc_fwd_pair: null pointer");
+  ConvPlan pl;
+  int rc = plan_fwd(pl, d, FWD_PAIR, WsSlot{});
+  if (rc != CGAN_OK) return rc;
+  CGAN_REQUIRE(!d->has_bias || bias_padded, "conv2d_nhwc_fwd_pair: has_bias but bias is null");
+  CGAN_REQUIRE(!d->has_residual || residual3, "conv2d_nhwc_fwd_pair: has_residual but residual is null");
+  bind(pl.p, x3, packed_w3, d->has_bias ? bias_padded : nullptr, residual3, y3);
+  return launch_plan(pl, (hipStream_t)stream, "conv2d_nhwc_fwd_pair");
+}
+
+// Forward with training-mode BatchNorm statistics from the kernel's epilogue (round 3): see the header.
+extern "C" int32_t cgan_conv2d_stats_chunk_pixels(const CganConvDesc* d) {
+  ConvPlan pl;
+  if (plan_fwd(pl, d, FWD_STATS, WsSlot{}) != CGAN_OK) return 0;
+  return stats_chunk_pixels(pl);
+}
+
+extern "C" int cgan_conv2d_nhwc_fwd_stats(const void* x, const void* packed_w, const float* bias_padded, void* y,
+                                          float* partial, size_t partial_bytes, const CganConvDesc* d, void* stream) {
+  CGAN_REQUIRE(x && packed_w && y && partial, "conv2d_nhwc_fwd_stats: null pointer");
+  ConvPlan pl;
+  int rc = plan_fwd(pl, d, FWD_STATS, WsSlot{});
+  if (rc != CGAN_OK) return rc;
+  CGAN_REQUIRE(!d->has_bias || bias_padded, "conv2d_nhwc_fwd_stats: has_bias but bias is null");
+  const int ppb = stats_chunk_pixels(pl);
+  CGAN_REQUIRE(ppb > 0, "conv2d_nhwc_fwd_stats: this descriptor's kernel writes no statistics "
+                        "(cgan_conv2d_stats_chunk_pixels returned 0)");
+  const size_t need = (size_t)(pl.p.npix / ppb) * pl.p.cout_s * 2 * sizeof(float);
+  if (partial_bytes < need) {
+    cgan_set_error("conv2d_nhwc_fwd_stats: partial buffer %zu B < required %zu B", partial_bytes, need);
+    return CGAN_ERR_WORKSPACE;
+  }
+  bind(pl.p, x, packed_w, d->has_bias ? bias_padded : nullptr, nullptr, y);
+  pl.p.stats = partial;
+  return launch_plan(pl, (hipStream_t)stream, "conv2d_nhwc_fwd_stats");
+}
+
+static size_t dgrad_packed_fragments(const ConvParams& p) {
+  if (!p.cls_s) return (size_t)p.ctiles * p.ksteps * 64;
+  size_t ks = 0;
+  for (int c = 0; c < p.cls_s * p.cls_s; ++c) ks += cls_ksteps(p.cls_s, p.kh, p.kw, p.cls_pad, p.cg, c);
+  return (size_t)p.ctiles * ks * 64;
+}
+
+// the data-gradient operator's layout follows the plan: sub-pixel, one block per parity class (cls_s, on either kernel), or dense
+extern "C" size_t cgan_conv2d_dgrad_packed_weight_bytes(const CganConvDesc* fwd) {
+  ConvPlan pl;
+  if (plan_dgrad(pl, fwd, RES_NONE, WsSlot{}) != CGAN_OK) return 0;
+  if (pl.route == ROUTE_SUBPIXEL) {
+    const Conv3x3LdsArgs a = lds_args(pl);
+    return (size_t)a.ctiles * a.ksteps * 64 * 16;
+  }
+  const size_t fr = dgrad_packed_fragments(pl.p);
+  return (fr ? fr : 64) * 16;
+}
+
+extern "C" int cgan_conv2d_pack_weight_dgrad(const float* w_oihw, const float* sigma, void* packed,
+                                             const CganConvDesc* fwd, void* stream) {
+  ConvPlan pl;
+  int rc = plan_dgrad(pl, fwd, RES_NONE, WsSlot{});
+  if (rc != CGAN_OK) return rc;
+  CGAN_REQUIRE(w_oihw && packed, "conv2d_pack_weight_dgrad: null pointer");
+  const ConvParams& p = pl.p;
+  const CganConvDesc& t = pl.d;
+  hipStream_t s = (hipStream_t)stream;
+  if (pl.route == ROUTE_SUBPIXEL) {
+    const int cin_p = lds_args(pl).cin_p;
+    const int tot = 9 * (cin_p / 32) * 64;
+    if (fwd->dtype == CGAN_F16)
+      hipLaunchKernelGGL(pack_dgrad_subpixel_kernel<F16>, dim3(ceil_div(tot, 256)), dim3(256), 0, s, w_oihw, sigma,
+                         (uint16_t*)packed, fwd->c_out, fwd->c_in, cin_p);
+    else
+      hipLaunchKernelGGL(pack_dgrad_subpixel_kernel<BF16>, dim3(ceil_div(tot, 256)), dim3(256), 0, s, w_oihw, sigma,
+                         (uint16_t*)packed, fwd->c_out, fwd->c_in, cin_p);
+  } else if (p.cls_s) {
+    int max_ks = 1;
+    for (int c = 0; c < p.cls_s * p.cls_s; ++c) {
+      const int k = cls_ksteps(p.cls_s, p.kh, p.kw, p.cls_pad, p.cg, c);
+      max_ks = k > max_ks ? k : max_ks;
+    }
+    const int tot = p.ctiles * max_ks * 64;
+    const dim3 grid(ceil_div(tot, 256) < 1024 ? ceil_div(tot, 256) : 1024, p.cls_s * p.cls_s);
+    if (fwd->dtype == CGAN_F16)
+      hipLaunchKernelGGL(pack_dgrad_classes_kernel<F16>, grid, dim3(256), 0, s, w_oihw, sigma, (uint16_t*)packed, t.c_out,
+                         t.c_in, p.cin_p, t.kh, t.kw, p.ctiles, p.cls_s, p.cls_pad);
+    else
+      hipLaunchKernelGGL(pack_dgrad_classes_kernel<BF16>, grid, dim3(256), 0, s, w_oihw, sigma, (uint16_t*)packed, t.c_out,
+                         t.c_in, p.cin_p, t.kh, t.kw, p.ctiles, p.cls_s, p.cls_pad);
+  } else {
+    const int total = p.ctiles * p.ksteps * 64;
+    const int blocks = ceil_div(total, 256) < 2048 ? ceil_div(total, 256) : 2048;
+    // rows = forward c_in, K channels = forward c_out
+    if (fwd->dtype == CGAN_F16)
+      hipLaunchKernelGGL(pack_conv_weight_kernel<F16>, dim3(blocks), dim3(256), 0, s, w_oihw, (const float*)nullptr, sigma,
+                         (uint16_t*)packed, (float*)nullptr, t.c_out, t.c_in, p.cin_p, t.kh, t.kw, p.ctiles, p.ksteps, 1);
+    else
+      hipLaunchKernelGGL(pack_conv_weight_kernel<BF16>, dim3(blocks), dim3(256), 0, s, w_oihw, (const float*)nullptr, sigma,
+                         (uint16_t*)packed, (float*)nullptr, t.c_out, t.c_in, p.cin_p, t.kh, t.kw, p.ctiles, p.ksteps, 1);
+  }
+  CGAN_CHECK_LAUNCH("conv2d_pack_weight_dgrad");
+  return CGAN_OK;
+}
+
+// ws: the split-K workspace the launch in question would find (a split-K launch needs its stream's binding)
+static int kernel_kind_impl(const CganConvDesc* d, int32_t bwd_data, const WsSlot& ws) {
+  ConvPlan pl;
+  const int rc = bwd_data ? plan_dgrad(pl, d, RES_NONE, ws) : plan_fwd(pl, d, FWD_PLAIN, ws);
+  return rc != CGAN_OK ? rc : route_family(pl.route);
+}
+
+// the kernel a launch of this descriptor on ``stream`` (of the current device) runs: that stream's workspace decides split-K
+extern "C" int cgan_conv2d_kernel_kind_on(const CganConvDesc* d, int32_t bwd_data, void* stream) {
+  return kernel_kind_impl(d, bwd_data, ws_lookup(stream));
+}
+// (kept for callers without a stream at hand: answers for the largest workspace bound on the current device)
+extern "C" int cgan_conv2d_kernel_kind(const CganConvDesc* d, int32_t bwd_data) {
+  return kernel_kind_impl(d, bwd_data, WsSlot{0, nullptr, nullptr, ws_max_bytes()});
+}
+
+// res: dx_add (RES_ADD, RES_ADD_RELU) or relu_out (RES_RELU); relu_out: RES_ADD_RELU
+static int bwd_data_impl(const void* dy, const void* packed_w_dgrad, const void* res, const void* relu_out, void* dx,
+                         const CganConvDesc* fwd, void* stream, int res_mode) {
+  CGAN_REQUIRE(dy && packed_w_dgrad && dx, "conv2d_nhwc_bwd_data: null pointer");
+  ConvPlan pl;
+  int rc = plan_dgrad(pl, fwd, res_mode, ws_lookup(stream));
+  if (rc != CGAN_OK) return rc;
+  bind(pl.p, dy, packed_w_dgrad, nullptr, res, dx);
+  if (pl.p.has_res == 3) pl.p.res2 = (const uint16_t*)relu_out;
+  rc = launch_plan(pl, (hipStream_t)stream, "conv2d_nhwc_bwd_data");
+  if (rc != CGAN_OK || res_mode != RES_ADD_RELU || pl.p.has_res == 3) return rc;
+  // the unfused form: the ReLU derivative as a pass of its own over dx, in place (element i is read and written by the
+  // same thread)
+  return cgan_act_bwd(relu_out, dx, dx, fwd->dtype, CGAN_ACT_RELU, 0.f,
+                      (int64_t)fwd->n * fwd->h_in * fwd->w_in * cgan_cs(fwd->c_in), stream);
 }
 
 extern "C" int cgan_conv2d_nhwc_bwd_data(const void* dy, const void* packed_w_dgrad, void* dx, const CganConvDesc* fwd,
                                          void* stream) {
-  return bwd_data_impl(dy, packed_w_dgrad, nullptr, dx, fwd, stream);
+  return bwd_data_impl(dy, packed_w_dgrad, nullptr, nullptr, dx, fwd, stream, RES_NONE);
 }
 
 extern "C" int cgan_conv2d_nhwc_bwd_data_relu(const void* dy, const void* packed_w_dgrad, const void* relu_out, void* dx,
                                               const CganConvDesc* fwd, void* stream) {
   CGAN_REQUIRE(relu_out != nullptr, "conv2d_nhwc_bwd_data_relu: null pointer");
-  return bwd_data_impl(dy, packed_w_dgrad, relu_out, dx, fwd, stream, 2);
+  return bwd_data_impl(dy, packed_w_dgrad, relu_out, nullptr, dx, fwd, stream, RES_RELU);
 }
 
-// dx = [relu_out > 0] * (data gradient + dx_add).  Fused (one launch, has_res = 3) where the dispatcher's kernel for this
-// descriptor has the shared store path; elsewhere the add rides in the epilogue and the ReLU derivative is a pass of its own
-// over dx (cgan_act_bwd, in place: element i is read and written by the same thread) -- same values either way.
+// dx = [relu_out > 0] * (data gradient + dx_add): one launch (has_res = 3) where the plan's GEMM kernel has the shared store
+// path, else the add in the epilogue and the ReLU derivative in a pass of its own -- same values either way.
 extern "C" int cgan_conv2d_nhwc_bwd_data_add_relu(const void* dy, const void* packed_w_dgrad, const void* dx_add,
                                                   const void* relu_out, void* dx, const CganConvDesc* fwd, void* stream) {
   CGAN_REQUIRE(dx_add != nullptr && relu_out != nullptr, "conv2d_nhwc_bwd_data_add_relu: null pointer");
-  ConvParams p;
-  CganConvDesc t;
-  int rc = dgrad_params(p, fwd, &t);
-  if (rc != CGAN_OK) return rc;
-  const bool plain = fwd->stride == 1 && p.pad >= 0 && t.h_in + 2 * p.pad - t.dilation * (t.kh - 1) == t.h_out &&
-                     t.w_in + 2 * p.pad - t.dilation * (t.kw - 1) == t.w_out;
-  CGAN_REQUIRE(plain, "conv2d_nhwc_bwd_data_add_relu: only for stride-1 'same' convolutions");
-  p.res = (const uint16_t*)dx_add; p.has_res = 1; p.res_ups = 0;
-  t.has_residual = 1; t.pad = p.pad;
-  if (select_conv_kernel(p, &t) == CGAN_CONV_KERNEL_GEMM && conv_gemm_res2_ok(gemm_args(p), fwd->dtype))
-    return bwd_data_impl(dy, packed_w_dgrad, dx_add, dx, fwd, stream, 3, relu_out);
-  rc = bwd_data_impl(dy, packed_w_dgrad, dx_add, dx, fwd, stream);
-  if (rc != CGAN_OK) return rc;
-  return cgan_act_bwd(relu_out, dx, dx, fwd->dtype, CGAN_ACT_RELU, 0.f,
-                      (int64_t)fwd->n * fwd->h_in * fwd->w_in * cgan_cs(fwd->c_in), stream);
+  return bwd_data_impl(dy, packed_w_dgrad, dx_add, relu_out, dx, fwd, stream, RES_ADD_RELU);
 }
 
 extern "C" int cgan_conv2d_nhwc_bwd_data_add(const void* dy, const void* packed_w_dgrad, const void* dx_add, void* dx,
                                              const CganConvDesc* fwd, void* stream) {
   CGAN_REQUIRE(dx_add != nullptr, "conv2d_nhwc_bwd_data_add: null pointer");
-  return bwd_data_impl(dy, packed_w_dgrad, dx_add, dx, fwd, stream);
+  return bwd_data_impl(dy, packed_w_dgrad, dx_add, nullptr, dx, fwd, stream, RES_ADD);
 }

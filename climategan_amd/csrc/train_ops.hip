@@ -20,10 +20,11 @@ __device__ __forceinline__ float act_grad_from_out(float out, int act, float slo
   }
 }
 
-// dx = dy * act'(.)   (16-bit NHWC storage, 8 elements per thread)
+// dx = dy * act'(.)   (16-bit NHWC storage, 8 elements per thread).  dy and dx may be the same buffer (not __restrict__):
+// the unfused form of cgan_conv2d_nhwc_bwd_data_add_relu runs in place.
 template <typename T>
-__global__ void act_bwd_kernel(const uint16_t* __restrict__ out, const uint16_t* __restrict__ dy,
-                               uint16_t* __restrict__ dx, int act, float slope, long groups) {
+__global__ void act_bwd_kernel(const uint16_t* __restrict__ out, const uint16_t* dy, uint16_t* dx, int act, float slope,
+                               long groups) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
     const u32x4 o = CGAN_LD_STREAM(reinterpret_cast<const u32x4*>(out) + i);
     const u32x4 g = CGAN_LD_STREAM(reinterpret_cast<const u32x4*>(dy) + i);

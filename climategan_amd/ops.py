@@ -1091,11 +1091,13 @@ def conv2d_bwd_data(dy: NHWC, w: torch.Tensor, x_shape, stride=1, pad=0, dilatio
     padding: data gradient of the pad-0 conv over the padded extent, folded back by the reflection's adjoint.
     ``add``: another gradient contribution of the same input tensor, summed in the kernel's epilogue (stride-1 'same'
     convolutions with zero padding; otherwise by a separate pass)."""
+    # stride-1 'same' convolutions with zero padding: ``add`` / ``relu_out`` ride in the kernel's epilogue
+    same = stride == 1 and pad_mode == PAD_ZERO and 2 * pad == dilation * (w.shape[2] - 1) and w.shape[2] == w.shape[3]
     if relu_out is not None:
         # ``relu_out``: the forward INPUT map, itself the output of a ReLU -- the kernel's epilogue applies that ReLU's
         # derivative (dx * [relu_out > 0]); where the fused form does not apply, the separate pass does
         # (with ``add``: dx = [relu_out > 0] * (data gradient + add), cgan_conv2d_nhwc_bwd_data_add_relu)
-        if not (stride == 1 and pad_mode == PAD_ZERO and 2 * pad == dilation * (w.shape[2] - 1) and w.shape[2] == w.shape[3]):
+        if not same:
             dx = conv2d_bwd_data(dy, w, x_shape, stride, pad, dilation, sigma, pad_mode, add=add, prepacked=prepacked)
             return act_bwd(relu_out, dx, ACT_RELU)
     per_sample = max(dy.t.nbytes // max(dy.n, 1), (x_shape[1] + 2 * pad) * (x_shape[2] + 2 * pad) * cs8(w.shape[1]) * 2)
@@ -1107,8 +1109,7 @@ def conv2d_bwd_data(dy: NHWC, w: torch.Tensor, x_shape, stride=1, pad=0, dilatio
             NHWC(dy.t[lo:lo + cnt], dy.c), w, (cnt, x_shape[1], x_shape[2]), stride, pad, dilation, sigma, pad_mode,
             NHWC(add.t[lo:lo + cnt], add.c) if add is not None else None, prepacked,
             NHWC(relu_out.t[lo:lo + cnt], relu_out.c) if relu_out is not None else None))
-    if add is not None and not (stride == 1 and pad_mode == PAD_ZERO and 2 * pad == dilation * (w.shape[2] - 1)
-                                and w.shape[2] == w.shape[3]):
+    if add is not None and not same:
         dx = conv2d_bwd_data(dy, w, x_shape, stride, pad, dilation, sigma, pad_mode, prepacked=prepacked)
         return NHWC(dx.t + add.t, dx.c)
     if pad_mode == PAD_REFLECT and pad > 0:

@@ -115,6 +115,9 @@ int cgan_conv2d_nhwc_fwd_stats(const void* x, const void* packed_w, const float*
  * the selection is a pure function of the descriptor: CGAN_CONV_KERNEL_GENERAL (gather implicit GEMM, conv_mfma.hip),
  * _LDS3X3 (spatially tiled 3x3, conv3x3_lds.hip) or _GEMM (wide-layer implicit GEMM, conv_gemm.hip); negative = the
  * descriptor is invalid.  Measurement aid: bench.py brackets the launches of one kernel family with events.
+ * bwd_data = 1 answers for cgan_conv2d_nhwc_bwd_data.  Its residual forms (_add, _relu, _add_relu) run the same kernel,
+ * except where that is the small-cin kernel (first layers, 8 storage channels: _LDS3X3), which has no residual epilogue:
+ * those run the general kernel (_GENERAL) instead.
  * One run-time input besides the descriptor: the small-grid / long-K layers run as split-K launches of the GEMM kernel only
  * when the launch stream has a workspace bound that holds their partial tiles (cgan_conv2d_bind_workspace, below) -- so the
  * kernel, and with it the fp32 summation order, of such a layer can change with the batch size (partials outgrow the

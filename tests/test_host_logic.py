@@ -51,6 +51,73 @@ def test_host_side_validation_without_gpu(lib):
     assert lib.cgan_spectral_norm_workspace_bytes(640, 5760) == (20 * 5760 + 5760 + 640 + 4) * 4
 
 
+# (descriptor, kernel family forward / data gradient without and with a split-K workspace, statistics chunk, packed bytes of
+# the forward / data-gradient operator).  Family: 0 general gather, 1 tiled 3x3 / small-cin / sub-pixel, 2 GEMM family.
+_ROUTE_CASES = [
+    # dt, n, h, w, cin, cout, k, stride, pad, dil, pad_mode, extra      fam ws=0  fam ws   stats  packed   dgrad packed
+    ((1, 8, 80, 80, 256, 256, 3, 1, 1, 1, 0, {}), (2, 2), (2, 2), 64, 1179648, 1179648),                 # wide GEMM
+    ((1, 8, 80, 80, 1024, 256, 1, 1, 0, 1, 0, {"has_bias": False}), (2, 2), (2, 2), 64, 524288, 524288),
+    ((0, 8, 80, 80, 256, 1024, 1, 1, 0, 1, 0, {}), (2, 2), (2, 2), 64, 524288, 524288),
+    ((0, 8, 80, 80, 256, 1024, 1, 1, 0, 1, 0, {"has_bias": False}), (2, 2), (2, 2), 128, 524288, 524288),  # choose(): no bias
+    ((0, 8, 80, 80, 256, 256, 3, 1, 1, 1, 0, {"act": 1}), (2, 2), (2, 2), 0, 1179648, 1179648),         # act: no statistics
+    ((1, 2, 160, 160, 64, 64, 3, 1, 1, 1, 1, {"act": 1}), (1, -1), (1, -1), 0, 73728, 0),             # tiled 3x3, reflect
+    ((0, 2, 80, 80, 128, 128, 3, 1, 1, 1, 0, {"in_upsample": True}), (1, 1), (1, 1), 0, 294912, 294912),
+    ((1, 4, 640, 640, 3, 64, 7, 2, 3, 1, 0, {}), (1, 0), (1, 0), 0, 53248, 100352),                     # small-cin stem
+    ((1, 2, 256, 256, 64, 3, 7, 1, 3, 1, 0, {}), (0, 1), (0, 1), 0, 100352, 53248),                     # small-cin dgrad
+    ((1, 2, 640, 640, 4, 64, 4, 2, 1, 1, 0, {"act": 2}), (1, 1), (1, 1), 0, 16384, 18432),              # sub-pixel dgrad
+    ((1, 2, 40, 40, 2048, 256, 3, 1, 4, 4, 0, {}), (0, 2), (2, 2), 0, 9437184, 9437184),                # split-K forward
+    ((0, 1, 16, 16, 24, 40, 3, 1, 1, 1, 0, {}), (0, 0), (0, 0), 0, 27648, 36864),                       # general
+    ((1, 2, 10, 10, 640, 640, 3, 1, 1, 1, 0, {}), (0, 0), (2, 2), 0, 7372800, 7372800),                 # split-K both
+    ((1, 2, 19, 19, 512, 1, 4, 1, 1, 1, 0, {}), (0, 0), (2, 0), 0, 262144, 131072),                     # PatchGAN head
+    ((1, 2, 32, 32, 64, 128, 4, 2, 1, 1, 0, {}), (0, 2), (2, 2), 0, 262144, 262144),                    # parity classes
+    ((0, 2, 16, 16, 256, 512, 1, 2, 0, 1, 0, {}), (0, 2), (0, 2), 0, 262144, 262144),
+    ((1, 2, 33, 33, 64, 64, 3, 2, 2, 2, 0, {}), (0, 0), (2, 0), 0, 73728, 73728),                       # zero insertion
+]
+
+
+@pytest.mark.parametrize("case", _ROUTE_CASES, ids=lambda c: "x".join(map(str, c[0][1:10])))
+def test_conv_dispatch_queries_pin_the_routes(lib, case):
+    """The host-side queries of the convolution dispatcher (kernel family of the forward and the data gradient, statistics
+    chunk, packed operator sizes) for one descriptor per launch route.  The split-K routes need a workspace on the launch
+    stream: a placeholder binding on a stream handle of this test's own (the lookup never dereferences either)."""
+    from climategan_amd import ops
+
+    (dt, n, h, w, cin, cout, k, stride, pad, dil, pad_mode, extra), fam, fam_ws, stats, nbytes, dbytes = case
+    d = ops._conv_desc(dt, n, h, w, cin, cout, k, k, stride, pad, dil, pad_mode, **extra)
+    r = ctypes.byref(d)
+    stream = ctypes.c_void_p(0x7E57_0000)
+
+    def families():
+        return tuple(lib.cgan_conv2d_kernel_kind_on(r, ctypes.c_int32(b), stream) for b in (0, 1))
+
+    assert families() == fam
+    assert lib.cgan_conv2d_bind_workspace(stream, ctypes.c_void_p(1 << 20), ctypes.c_size_t(64 << 20)) == 0
+    try:
+        assert families() == fam_ws
+    finally:
+        assert lib.cgan_conv2d_bind_workspace(stream, None, ctypes.c_size_t(0)) == 0
+    assert lib.cgan_conv2d_stats_chunk_pixels(r) == stats
+    assert lib.cgan_conv2d_packed_weight_bytes(r) == nbytes
+    assert lib.cgan_conv2d_dgrad_packed_weight_bytes(r) == dbytes
+
+
+def test_conv_with_empty_output_is_refused_before_planning(lib):
+    """A 4x4 / stride-1 / pad-1 conv of a 1x1 map has no output pixels (the coarsest scale of a multi-scale discriminator);
+    its empty output tensor arrives as a null pointer.  The launch refuses it before the plan, whose split-K sizing would
+    divide by the zero pixel blocks once the stream has a workspace bound."""
+    from climategan_amd._lib import ConvDesc
+
+    d = ConvDesc(1, 1, 1, 1, 128, 1, 4, 4, 1, 1, 1, 0, 0, 0, 0, 0, 0.2, 1, 0, 0)
+    stream = ctypes.c_void_p(0x7E57_0000)
+    one = ctypes.c_void_p(16)
+    assert lib.cgan_conv2d_bind_workspace(stream, ctypes.c_void_p(1 << 20), ctypes.c_size_t(64 << 20)) == 0
+    try:
+        assert lib.cgan_conv2d_nhwc_fwd(one, one, one, None, None, ctypes.byref(d), stream) < 0
+        assert b"null pointer" in lib.cgan_last_error()
+    finally:
+        assert lib.cgan_conv2d_bind_workspace(stream, None, ctypes.c_size_t(0)) == 0
+
+
 def test_rccl_entry_points_refuse_before_load(lib):
     """The gradient-bucket collective of the C ABI loads RCCL at run time: before cgan_rccl_load has succeeded every entry
     point fails with a message (no crash, no link-time dependency: this test runs on a box without a GPU), and a bad path
