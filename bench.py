@@ -11,7 +11,12 @@ batch of 32 per domain -- SURVEY 8d M1: "at 1/2/4/8 GPUs, global bs 32 (4/GPU at
   second over all ranks (a step consumes ``bs`` samples from each of the three domains; the raw-image
   figure is 3x and reported next to it); ``scaling`` is "strong": the job's work per step does not change with N.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up, runs the W warm-up and the K timed steps (with the
+``roofline`` launch brackets on every EVENT_EVERY-th timed step, as ever), writes ``--dump-outputs`` and prints the line.
+``--full`` adds everything that takes time of its own after the timed steps: ``roofline_all_mfma`` (extra steps with every
+MFMA launch bracketed), the live ``roofline.traffic`` passes, the sub-blocks, and the CPU baselines.
 
 ``--dump-outputs DIR`` writes what the last timed headline step computed (``dump_outputs``) as DIR/<name>.npy; the step's
 random draws are seeded, so two builds run with the same arguments can be compared output for output.
@@ -29,6 +34,7 @@ The JSON line also carries
                 with >= 64 output channels; MFMA-bound): every launch inside the timed region is bracketed by events on
                 the launch stream, achieved = algorithmic FLOPs (2 * output pixels * c_out * c_in * taps, from the call's
                 own descriptor) / summed duration;
+and, with ``--full`` (a plain run reports ``cpu_baseline`` as null and ``sub_blocks`` empty):
   cpu_baseline  the oracle's CPU restatement of the same step (``oracle.cpu_ref.joint_train_step``, torch fp32 autograd)
                 on a bounded sample -- one step at 1 sample per domain, 640x640 -- on the host cores (rank 0, N = 1);
   sub_blocks    the other BASELINE configurations on the same box, each with >= 20 timed steps: configs[1] Painter
@@ -1061,16 +1067,22 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: roofline_all_mfma, the live "
+                         "roofline.traffic passes, the sub-blocks and the CPU baselines (the --no-* / --*-steps options "
+                         "below trim a --full run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-launch-events", action="store_true", help="do not bracket the conv_gemm launches (no roofline)")
     ap.add_argument("--conv-table", default="", help="write the per-shape table of the bracketed conv_gemm launches here")
     ap.add_argument("--call-log", default="", help="write (C-ABI entry point, algorithmic bytes) of every call of one step here")
-    ap.add_argument("--mfma-table-steps", type=int, default=2,
-                    help="extra single-stream steps after the timed region with EVERY MFMA-kernel launch bracketed (0 = skip)")
-    ap.add_argument("--sub-steps", type=int, default=20, help="timed steps of each sub-block (0 = skip the sub-blocks)")
+    ap.add_argument("--mfma-table-steps", type=int, default=None,
+                    help="extra single-stream steps after the timed region with EVERY MFMA-kernel launch bracketed (0 = skip; "
+                         "default 2 with --full, --conv-table or --call-log, else 0)")
+    ap.add_argument("--sub-steps", type=int, default=None,
+                    help="timed steps of each sub-block (0 = skip the sub-blocks; default 20 with --full, else 0)")
     ap.add_argument("--sub-warm-seconds", type=float, default=-1.0,
                     help="minimum warm-up time of the millisecond-step blocks (Painter forward, apply_events): default 1 s in "
-                         "the default run, 0 with --only")
+                         "the sub-blocks after the headline, 0 with --only")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not re-measure roofline.traffic with two rocprofv3 --pmc child passes (report the committed summary)")
     ap.add_argument("--ddp-bucket-mb", type=float, default=0.0, help="N > 1: gradient bucket size of the reducer (default 25)")
@@ -1090,6 +1102,14 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.only:
         ap.error("--dump-outputs writes the headline step's outputs; it does not combine with --only")
+    if args.full and args.only:
+        ap.error("--full adds to the headline run; it does not combine with --only")
+    if args.mfma_table_steps is None:
+        args.mfma_table_steps = 2 if (args.full or args.conv_table or args.call_log) else 0
+    if args.sub_steps is None:
+        args.sub_steps = 20 if args.full else 0
+    with_cpu_baseline = args.full and not args.no_cpu_baseline
+    with_live_traffic = args.full and not args.no_live_traffic
 
     # multi-GPU knobs reach the reducer / RCCL through the environment (read at communicator / reducer construction)
     if args.ddp_bucket_mb > 0:
@@ -1340,7 +1360,7 @@ def main():
     T.close()
     del T, batch
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_live_traffic and res.get("roofline"):
+    if rank == 0 and world == 1 and with_live_traffic and res.get("roofline"):
         lps = res["roofline"]["launches_per_step"]
         live = live_traffic(lps, args.global_batch)
         if live is not None:
@@ -1354,7 +1374,7 @@ def main():
     # collective-bearing path less that could leave ranks waiting on each other after the line is out
     if args.sub_steps > 0 and world == 1:
         blocks = (("painter_forward", lambda: painter_block(args.sub_steps, 5, rank, world, device, dtype, dist, barrier,
-                                                           world == 1 and not args.no_cpu_baseline)),
+                                                           world == 1 and with_cpu_baseline)),
                   ("masker_train", lambda: masker_block(args.sub_steps, 3, rank, world, device, dtype, dist, barrier,
                                                         args.conv_table + ".masker" if args.conv_table else "")),
                   ("per_gpu_slice", lambda: slice_block(args.sub_steps, 5, rank, device, dtype, barrier)),
@@ -1376,7 +1396,7 @@ def main():
                                                     "(sub_blocks.painter_forward)", "bound": "mfma", "achieved": ts["achieved"],
                                           "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ts["frac"],
                                           "frac_all_23_launches": pf["roofline"]["frac"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and with_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline_train()
             except Exception as e:

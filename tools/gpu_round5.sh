@@ -6,8 +6,8 @@ mkdir -p gpurun_out
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 TAG=${1:-r05}
-CPUB=${FULL:+}
-[ -z "$FULL" ] && CPUB=--no-cpu-baseline
+CPUB=--full
+[ -z "$FULL" ] && CPUB="--full --no-cpu-baseline"
 (timeout 300 python __graft_entry__.py smoke 2>&1 | tail -2) > gpurun_out/smoke.log 2>&1
 (timeout 1700 python bench.py $CPUB --conv-table gpurun_out/conv_table_$TAG.txt 2>&1 | tail -1) > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
 (timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$TAG -o $TAG -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --sub-steps 0 --mfma-table-steps 0 2>&1 | tail -1) > gpurun_out/rocprof_$TAG.log 2>&1
