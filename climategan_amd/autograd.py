@@ -441,6 +441,40 @@ class PainterHeadsFn(torch.autograd.Function):
         return ops.painter_heads_bwd(dd, dv, m).t, None, None, None, None
 
 
+class PainterHeadsDiffAugFn(torch.autograd.Function):
+    """PainterHeadsFn with DiffAugment on the discriminator half (ops.painter_heads_diffaug); gradient to ``fake`` only."""
+
+    @staticmethod
+    def forward(ctx, fake_t, x, m, color, geo, flags, cut_hw, want_vgg):
+        d_in, v_in = ops.painter_heads_diffaug(ops.NHWC(fake_t, 3), x, m, fake_t.dtype, color, geo, flags, cut_hw, want_vgg)
+        ctx.save_for_backward(m, color, geo)
+        ctx.aug = (flags, cut_hw, want_vgg)
+        return d_in.t, (v_in.t if want_vgg else fake_t.new_empty(0))
+
+    @staticmethod
+    def backward(ctx, dd_t, dv_t):
+        m, color, geo = ctx.saved_tensors
+        flags, cut_hw, want_vgg = ctx.aug
+        dd = ops.NHWC(dd_t.contiguous(), 4) if dd_t is not None else ops.NHWC(torch.zeros_like(dv_t), 4)
+        dv = ops.NHWC(dv_t.contiguous(), 6) if want_vgg and dv_t is not None else None
+        return ops.painter_heads_diffaug_bwd(dd, dv, m, color, geo, flags, cut_hw).t, None, None, None, None, None, None, None
+
+
+class DiffAugFn(torch.autograd.Function):
+    """DiffTransforms on an NCHW fp32 batch with fixed draws (ops.diffaug); gradient to the image."""
+
+    @staticmethod
+    def forward(ctx, x, color, geo, flags, cut_hw):
+        ctx.save_for_backward(color, geo)
+        ctx.aug = (flags, cut_hw)
+        return ops.diffaug(x, color, geo, flags, cut_hw)
+
+    @staticmethod
+    def backward(ctx, dy):
+        color, geo = ctx.saved_tensors
+        return ops.diffaug_bwd(dy, color, geo, *ctx.aug), None, None, None, None
+
+
 class AvgPool3x3s2Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_t, c):

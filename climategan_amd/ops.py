@@ -1523,6 +1523,81 @@ def painter_heads_bwd(d_d_in: Optional[NHWC], d_vgg_in: Optional[NHWC], m: torch
     return NHWC(dfake, 3)
 
 
+# DiffAugment (reference transforms.py:494-626): flag bits of the C ABI (CGAN_DA_*) and the per-image workspace
+DA_BRIGHTNESS, DA_CONTRAST, DA_SATURATION, DA_TRANSLATION, DA_CUTOUT = 1, 2, 4, 8, 16
+DIFFAUG_PARTS = 256
+
+
+def _diffaug_args(color, geo, flags, cut_hw):
+    """color [n, 3] fp32 raw draws (brightness, contrast, saturation), geo [n, 4] int64 (tx, ty, ox, oy); the per-image
+    partial sums of the contrast mean go to a private workspace (not the chunk arena: it is no part of the result)."""
+    if (color.dtype != torch.float32 or geo.dtype != torch.int64 or color.shape[1:] != (3,) or geo.shape[1:] != (4,)
+            or not color.is_contiguous() or not geo.is_contiguous()):
+        raise RuntimeError("diffaug: color must be a contiguous [n, 3] float32 and geo a contiguous [n, 4] int64 tensor, "
+                           "got %s %s / %s %s"
+                           % (tuple(color.shape), color.dtype, tuple(geo.shape), geo.dtype))
+    ws = torch.empty((color.shape[0], DIFFAUG_PARTS), dtype=torch.float32, device=color.device)
+    return (_ptr(color), _ptr(geo), int(flags), int(cut_hw[0]), int(cut_hw[1])), ws
+
+
+@_batch_chunked("x", "color", "geo")
+def diffaug(x: torch.Tensor, color: torch.Tensor, geo: torch.Tensor, flags: int, cut_hw) -> torch.Tensor:
+    """DiffTransforms on an NCHW fp32 batch with the given per-image draws (``flags``: DA_* bits; ``cut_hw``: the cutout
+    box size).  Returns a new NCHW fp32 tensor."""
+    _need_cuda(x, color, geo)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("diffaug: x must be an NCHW float32 tensor, got %s %s" % (tuple(x.shape), x.dtype))
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    y = _empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    da, ws = _diffaug_args(color, geo, flags, cut_hw)
+    _lib.check(_lib.load().cgan_diffaug_fwd(_ptr(x), _ptr(y), *da, n, c, h, w, _ptr(ws), _stream()), "cgan_diffaug_fwd")
+    return y
+
+
+@_batch_chunked("dy", "color", "geo")
+def diffaug_bwd(dy: torch.Tensor, color: torch.Tensor, geo: torch.Tensor, flags: int, cut_hw) -> torch.Tensor:
+    _need_cuda(dy, color, geo)
+    dy = dy.contiguous().float()
+    n, c, h, w = dy.shape
+    dx = _empty((n, c, h, w), dtype=torch.float32, device=dy.device)
+    da, ws = _diffaug_args(color, geo, flags, cut_hw)
+    _lib.check(_lib.load().cgan_diffaug_bwd(_ptr(dy), _ptr(dx), *da, n, c, h, w, _ptr(ws), _stream()), "cgan_diffaug_bwd")
+    return dx
+
+
+@_batch_chunked("fake", "x", "m", "color", "geo")
+def painter_heads_diffaug(fake: Optional[NHWC], x: torch.Tensor, m: torch.Tensor, dtype, color: torch.Tensor,
+                          geo: torch.Tensor, flags: int, cut_hw, want_vgg=False):
+    """painter_heads with DiffAugment on the discriminator half: d_in = [m | augment(p)]; the VGG input (when asked) is
+    the un-augmented p's, identical to painter_heads'."""
+    _need_cuda(x, m, fake.t if fake is not None else None, color, geo)
+    x = x.contiguous().float()
+    m = m.contiguous().float()
+    n, _, h, w = x.shape
+    d_in = _empty((n, h, w, 8), dtype=dtype, device=x.device)
+    v_in = _empty((n, h, w, 8), dtype=dtype, device=x.device) if want_vgg else None
+    da, ws = _diffaug_args(color, geo, flags, cut_hw)
+    _lib.check(_lib.load().cgan_painter_heads_diffaug_fwd(_ptr(fake.t if fake is not None else None), _ptr(x), _ptr(m),
+                                                          _ptr(d_in), _ptr(v_in), *da, _DT[dtype], n, h, w, _ptr(ws),
+                                                          _stream()), "cgan_painter_heads_diffaug_fwd")
+    return NHWC(d_in, 4), (NHWC(v_in, 6) if want_vgg else None)
+
+
+@_batch_chunked("d_d_in", "d_vgg_in", "m", "color", "geo")
+def painter_heads_diffaug_bwd(d_d_in: NHWC, d_vgg_in: Optional[NHWC], m: torch.Tensor, color: torch.Tensor,
+                              geo: torch.Tensor, flags: int, cut_hw) -> NHWC:
+    _need_cuda(d_d_in.t, m, color, geo)
+    m = m.contiguous().float()
+    n, h, w = d_d_in.n, d_d_in.h, d_d_in.w
+    dfake = _empty((n, h, w, 8), dtype=d_d_in.t.dtype, device=d_d_in.t.device)
+    da, ws = _diffaug_args(color, geo, flags, cut_hw)
+    _lib.check(_lib.load().cgan_painter_heads_diffaug_bwd(_ptr(d_d_in.t), _ptr(d_vgg_in.t if d_vgg_in is not None else None),
+                                                          _ptr(m), _ptr(dfake), *da, d_d_in.dtype_id, n, h, w, _ptr(ws),
+                                                          _stream()), "cgan_painter_heads_diffaug_bwd")
+    return NHWC(dfake, 3)
+
+
 @_batch_chunked("dy", out_bytes_per_sample=lambda g: g("in_hw")[0] * g("in_hw")[1] * g("dy").cs * 2)
 def avgpool3x3s2_bwd(dy: NHWC, in_hw) -> NHWC:
     _need_cuda(dy.t)

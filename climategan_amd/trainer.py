@@ -72,6 +72,7 @@ class Trainer:
         self.D = None
         self.is_setup = False
         self.has_painter = "p" in opts.tasks
+        self.diff_transforms = None      # set by setup() when gen.p.diff_aug.use (trainer.py:772-773)
         self.use_pl4m = False            # trainer.py:94; maybe_enable_pl4m() / run_epoch() switch it on at opts.gen.p.pl4m_epoch
         # the real and the simulated domain batch share the Masker's encoder / depth / segmentation launches (grouped
         # BatchNorm keeps the per-domain statistics of the reference's separate calls); False = one pass per domain
@@ -117,6 +118,9 @@ class Trainer:
         self.losses = get_losses(o, self.verbose, self.device)
         if o.train.lambdas.G.p.vgg == 0:
             self.losses["G"]["p"]["vgg"] = None
+        if "p" in o.tasks and o.gen.p.get("diff_aug", {}).get("use", False):          # trainer.py:772-773
+            from .transforms import DiffTransforms
+            self.diff_transforms = DiffTransforms(o.gen.p.diff_aug)
         g_params = [p for p in self.G.parameters() if p.requires_grad]
         d_params = [p for p in self.D.parameters() if p.requires_grad]
         # get_optimizer (trainer.py:758-767): groups / parameter order of the reference, so g_opt / d_opt state dicts are
@@ -163,8 +167,21 @@ class Trainer:
             self._gc_frozen = False
 
     # ------------------------------------------------------------------------------------------ training
+    def _diff_aug(self):
+        """The DiffTransforms to apply to the Painter discriminator's inputs, or None: ``gen.p.diff_aug.use`` off, or on with
+        every ``do_*`` off (the identity: no draw, no launch).  The transform is built by setup() (trainer.py:772-773); the
+        option switched on after setup has none to apply and is refused."""
+        if not self.opts.gen.p.get("diff_aug", {}).get("use", False):
+            return None
+        if self.diff_transforms is None:
+            raise NotImplementedError("gen.p.diff_aug.use was switched on after setup(): its DiffTransforms is built by "
+                                      "setup() (reference trainer.py:772-773); call setup() with the option on")
+        return self.diff_transforms if self.diff_transforms.active else None
+
     def _painter_terms(self, batch, for_g):
-        """D(cat_batch[real, fake]) on NHWC inputs built by the heads kernel; returns (real_d, fake_d, vgg pair)."""
+        """D(cat_batch[real, fake]) on NHWC inputs built by the heads kernel; returns (real_d, fake_d, vgg pair).  With
+        DiffAugment the heads kernels augment the discriminator half (the draws for the fake first, then for x:
+        trainer.py:1080-1081, 1320-1321); the VGG inputs stay un-augmented."""
         from .autograd import PainterHeadsFn
         from .tutils import divide_pred
 
@@ -177,12 +194,24 @@ class Trainer:
         else:
             with torch.no_grad():                                     # trainer.py:1076-1083
                 fake = self.G.paint_nhwc(m, x)
-        real_in, vgg_real = ops.painter_heads(None, x, m, dt, True, want_vgg)
-        if for_g:
-            fake_in_t, vgg_fake_t = PainterHeadsFn.apply(fake.t, x, m, True, want_vgg)
+        da = self._diff_aug()
+        if da is not None:
+            from .autograd import PainterHeadsDiffAugFn
+            n, _, h, w = x.shape
+            pf = da.draw(n, h, w, x.device)
+            px = da.draw(n, h, w, x.device)
+            real_in, vgg_real = ops.painter_heads_diffaug(None, x, m, dt, *px, want_vgg)
+            if for_g:
+                fake_in_t, vgg_fake_t = PainterHeadsDiffAugFn.apply(fake.t, x, m, *pf, want_vgg)
+            else:
+                fake_in_t, vgg_fake_t = ops.painter_heads_diffaug(fake, x, m, dt, *pf)[0].t, None
         else:
-            fake_in, _ = ops.painter_heads(fake, x, m, dt, True, False)
-            fake_in_t, vgg_fake_t = fake_in.t, None
+            real_in, vgg_real = ops.painter_heads(None, x, m, dt, True, want_vgg)
+            if for_g:
+                fake_in_t, vgg_fake_t = PainterHeadsFn.apply(fake.t, x, m, True, want_vgg)
+            else:
+                fake_in, _ = ops.painter_heads(fake, x, m, dt, True, False)
+                fake_in_t, vgg_fake_t = fake_in.t, None
         real_fake_cat = ops.NHWC(torch.cat([real_in.t, fake_in_t], dim=0), 4)            # trainer.py:1103,1363
         real_fake_d = self.D["p"](real_fake_cat, nhwc=True)
         real_d, fake_d = divide_pred(real_fake_d)
@@ -231,6 +260,10 @@ class Trainer:
             step_loss = step_loss + loss
         if aux:                                                                                       # :1289-1315
             step_loss = step_loss + self._painter_aux_terms(raw, x, m)
+        da = self._diff_aug()
+        if da is not None:                                                                            # :1319-1321
+            fake = da(fake)
+            x = da(x)
         fake_d_global = self.D["p"]["global"](fake)
         fake_d_local = self.D["p"]["local"](fake * m)
         real_d_global = self.D["p"]["global"](x)
@@ -249,9 +282,6 @@ class Trainer:
         """reference trainer.py:1256-1387 (the TV / context / reconstruction terms, lambdas 0 in defaults.yaml:293-300, come
         from one fused kernel on the pasted image, autograd.PainterAuxFn)."""
         lambdas = self.opts.train.lambdas
-        if self.opts.gen.p.get("diff_aug", {}).get("use", False):
-            raise NotImplementedError("gen.p.diff_aug (transforms.py:609 DiffTransforms: data augmentation, out of scope) "
-                                      "has no HIP path")
         if self.opts.dis.p.use_local_discriminator:
             return self._painter_loss_local_pair(multi_domain_batch["rf"])
         real_d, fake_d, vgg = self._painter_terms(multi_domain_batch["rf"], True)
@@ -274,13 +304,15 @@ class Trainer:
 
     def get_D_loss(self, multi_domain_batch):
         """reference trainer.py:1034-1160, Painter branch (1073-1107)."""
-        if self.opts.gen.p.get("diff_aug", {}).get("use", False):
-            raise NotImplementedError("gen.p.diff_aug has no HIP path")
         if self.opts.dis.p.use_local_discriminator:                                   # :1085-1099
             data = multi_domain_batch["rf"]["data"]
             x, m = data["x"], data["m"]
             with torch.no_grad():
                 fake = self.G.paint(m, x)
+                da = self._diff_aug()
+                if da is not None:                                                    # :1079-1081
+                    fake = da(fake)
+                    x = da(x)
             fake = fake.detach()
             crit = self.losses["D"]["p"]
             g_loss = crit(self.D["p"]["global"](fake), False, True) + crit(self.D["p"]["global"](x), True, True)

@@ -462,6 +462,37 @@ int cgan_painter_heads_fwd(const void* fake_nhwc, const float* x_nchw, const flo
                            int32_t dtype, int32_t n, int32_t h, int32_t w, void* stream);
 int cgan_painter_heads_bwd(const void* d_d_in, const void* d_vgg_in, const float* m_nchw, void* d_fake, int32_t dtype,
                            int32_t n, int32_t h, int32_t w, void* stream);
+/* DiffAugment (climategan/transforms.py:494-626, DiffTransforms; applied by trainer.py:1079-1081 on the D side and
+ * :1319-1321 on the G side when gen.p.diff_aug.use).  Per image n, in this order, each op only when its flag is set:
+ *   brightness  t + (rb - 0.5)                                      (:494-501)
+ *   contrast    (t - mean_chw(t)) (rc + 0.5) + mean_chw(t)          (:527-534; the mean of the brightened image)
+ *   saturation  (t - mean_c(t)) (2 rs) + mean_c(t)                  (:510-518; per-pixel mean over the channels)
+ *   translation out[i][j] = in[i + tx][j + ty], 0 where that lies outside the image (:580-606)
+ *   cutout      out = 0 on rows clamp(k + ox - cut_h / 2, 0, h - 1), k < cut_h, times the columns likewise (:544-577)
+ * color [n][3] = the raw draws (rb, rc, rs), fp32; geo [n][4] = (tx, ty, ox, oy), int64 (torch.randint's results);
+ * cut_h / cut_w = int(h * ratio + 0.5) / int(w * ratio + 0.5).  ws: CGAN_DIFFAUG_PARTS floats per image (per-image partial
+ * sums for the contrast mean and its backward, reduced in a fixed order: no atomics, run-to-run identical).
+ * diffaug_fwd / _bwd: NCHW fp32 x -> y and dy -> dx (any channel count).
+ * painter_heads_diffaug_fwd: cgan_painter_heads_fwd with the augmentation on the pasted image's discriminator half:
+ *   d_in = [m | augment(p)] (m neither jittered nor moved); vgg_in (may be NULL) = the UN-augmented p's, bit for bit
+ *   cgan_painter_heads_fwd's.  painter_heads_diffaug_bwd: d_fake = m * (augment_bwd(d_d_in[1..3]) + 127.5 m d_vgg_in[BGR -> RGB]). */
+#define CGAN_DA_BRIGHTNESS 1
+#define CGAN_DA_CONTRAST 2
+#define CGAN_DA_SATURATION 4
+#define CGAN_DA_TRANSLATION 8
+#define CGAN_DA_CUTOUT 16
+#define CGAN_DA_ALL 31
+#define CGAN_DIFFAUG_PARTS 256
+int cgan_diffaug_fwd(const float* x, float* y, const float* color, const int64_t* geo, int32_t flags, int32_t cut_h,
+                     int32_t cut_w, int32_t n, int32_t c, int32_t h, int32_t w, float* ws, void* stream);
+int cgan_diffaug_bwd(const float* dy, float* dx, const float* color, const int64_t* geo, int32_t flags, int32_t cut_h,
+                     int32_t cut_w, int32_t n, int32_t c, int32_t h, int32_t w, float* ws, void* stream);
+int cgan_painter_heads_diffaug_fwd(const void* fake_nhwc, const float* x_nchw, const float* m_nchw, void* d_in, void* vgg_in,
+                                   const float* color, const int64_t* geo, int32_t flags, int32_t cut_h, int32_t cut_w,
+                                   int32_t dtype, int32_t n, int32_t h, int32_t w, float* ws, void* stream);
+int cgan_painter_heads_diffaug_bwd(const void* d_d_in, const void* d_vgg_in, const float* m_nchw, void* d_fake,
+                                   const float* color, const int64_t* geo, int32_t flags, int32_t cut_h, int32_t cut_w,
+                                   int32_t dtype, int32_t n, int32_t h, int32_t w, float* ws, void* stream);
 /* backward of cgan_avgpool3x3s2_nhwc: dy [n][h_out][w_out][cs] -> dx [n][h_in][w_in][cs] */
 int cgan_avgpool3x3s2_bwd_nhwc(const void* dy, void* dx, int32_t dtype, int32_t n, int32_t c, int32_t h_in,
                                int32_t w_in, void* stream);

@@ -2,7 +2,8 @@
 --tasks p     Painter step, bs 8 per GPU: default Painter (latent 640, 7 up-samplings), 3-scale PatchGAN, GAN +
               feature-matching + VGG losses;
 --tasks dsmp  the joint Masker + Painter step of BASELINE metric M1 (domains r, s, rf; --bs samples per domain).
-Also: --wgrad-table / --conv-table (per-shape tables of the conv calls of one step), --cprofile (host side).
+Also: --wgrad-table / --conv-table (per-shape tables of the conv calls of one step), --cprofile (host side),
+--diff-aug (gen.p.diff_aug on with all three sub-options: the Painter discriminator's inputs augmented).
 
 usage (GPU box): python tools/bench_train.py [--bs 8] [--steps 6] [--dtype bf16] [--no-vgg]
 """
@@ -172,6 +173,8 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--no-vgg", action="store_true")
+    ap.add_argument("--diff-aug", action="store_true",
+                    help="gen.p.diff_aug.use with color jittering, translation and cutout on (defaults.yaml:158-164)")
     ap.add_argument("--tasks", default="p", help="'p' (Painter step) or 'dsmp' (joint Masker + Painter step: domains r, s, rf)")
     ap.add_argument("--conv-table", action="store_true", help="per-shape table of the forward / data-gradient conv calls of one step")
     ap.add_argument("--only", default="", choices=["", "G", "D"], help="time / profile only update_G or only update_D")
@@ -195,6 +198,8 @@ def main():
     opts.tasks = list(args.tasks)
     if args.no_vgg:
         opts.train.lambdas.G.p.vgg = 0
+    if args.diff_aug:
+        opts.gen.p.diff_aug.update(use=True, do_color_jittering=True, do_translation=True, do_cutout=True)
     T = Trainer(opts, device="cuda").setup(inference=False)
     for mod, seed in ((T.G, 0), (T.D, 1)):
         shapes = {k: tuple(v.shape) for k, v in mod.state_dict().items()}
@@ -262,8 +267,9 @@ def main():
         td += c - b
     dtot = time.perf_counter() - t0
     print(json.dumps({
-        "workload": "%s train step (update_G + update_D, ExtraAdam), %dx%d bs %d per domain %s, vgg=%s" % (
-            "Painter" if args.tasks == "p" else "joint Masker+Painter (domains r, s, rf)", args.size, args.size, args.bs, args.dtype, not args.no_vgg),
+        "workload": "%s train step (update_G + update_D, ExtraAdam), %dx%d bs %d per domain %s, vgg=%s%s" % (
+            "Painter" if args.tasks == "p" else "joint Masker+Painter (domains r, s, rf)", args.size, args.size, args.bs, args.dtype, not args.no_vgg,
+            ", diff_aug" if args.diff_aug else ""),
         "images_per_s": round(args.bs * args.steps / dtot, 2), "raw_images_per_s": round(args.bs * len(batch) * args.steps / dtot, 2), "ms_per_step": round(dtot / args.steps * 1e3, 1),
         "host_enqueue_ms": round(enqueue_ms, 1), "gpu_drain_after_enqueue_ms": round(drain_ms, 1),
         "update_G_ms": round(tg / args.steps * 1e3, 1), "update_D_ms": round(td / args.steps * 1e3, 1),
