@@ -101,7 +101,11 @@ _SIGNATURES = {
     "cgan_comm_destroy": (C.c_int, [_P]),
     "cgan_allreduce_bucket": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
     "cgan_seg_counts": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P]),
-    "cgan_resize_crop_geometry": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+    "cgan_mask_label_encode": (C.c_int, [_P] + [C.c_int32] * 10 + [_P, _P]),
+    "cgan_masker_eval_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "cgan_masker_eval": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                   _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "cgan_resize_crop_geometry":(C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cgan_resize_u8": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P,
                                  _P, C.c_size_t, _P]),

@@ -907,6 +907,42 @@ class Trainer:
         return 0
 
     # ------------------------------------------------------------------------------------------ checkpoints
+    @classmethod
+    def resume_from_path(cls, path, overrides={}, setup=True, inference=False, new_exp=False, device=None, verbose=1):
+        """reference trainer.py:337-394: a Trainer from a run directory -- the latest ``opts (i).yaml`` (utils.py:716-738,
+        843-871), ``overrides`` merged over it, ``train.resume = True``, then ``setup(inference)`` (which loads the
+        checkpoint).  The events come from this package's defaults (config.py; the reference reads shared/trainer/
+        events.yaml).  There is no comet logging here: ``new_exp`` is accepted and ignored."""
+        import re
+        from pathlib import Path
+
+        import numpy as np
+        import yaml
+
+        from .config import Opts, default_opts
+
+        p = Path(path).expanduser().resolve()
+        assert p.exists()
+        c = p / "checkpoints"
+        assert c.exists() and c.is_dir()
+        base = p / "opts.yaml"
+        found = list(p.glob("opts*(*).yaml"))
+        if found:                                    # get_latest_path: the largest "(i)" wins
+            latest = found[int(np.argmax([int(re.findall(r"\((.*?)\)", f.name)[-1]) for f in found]))]
+        else:
+            latest = base
+        assert latest.exists()
+        opts = Opts(yaml.safe_load(latest.read_text()))
+        opts.events = default_opts().events
+        opts = Opts(_merge(overrides, opts))
+        opts.train.resume = True
+        trainer = cls(opts, comet_exp=None, device=device, verbose=verbose)
+        if setup:
+            trainer.setup(inference=inference)
+            if not inference:                        # reference trainer.py:808-810 (the end of its training setup)
+                trainer.resume(False)
+        return trainer
+
     def update_learning_rates(self):
         """reference trainer.py:696-700 (called once per epoch by run_epoch, and epoch+1 times by resume)."""
         if self.g_scheduler is not None:

@@ -689,6 +689,35 @@ int cgan_resize_u8(const void* img_hwc_u8, int32_t h, int32_t w, int32_t c, int3
 int cgan_seg_counts(const void* pred, int32_t layout, int32_t dtype, int32_t n, int64_t hw, int32_t c,
                     const float* labels, unsigned long long* counts, void* stream);
 
+/* Masker evaluation on a labelled test set (eval_masker.py:168-229, 505-560; climategan/eval_metrics.py:133-542).
+ * mask_label_encode: crop_and_resize's label branch + encode_mask_label (data.py:255-271) for n RGB uint8 photos
+ *   [n][h][w][3]: nearest-neighbour resize to rows x cols (skimage 0.18.3 resize(order=0): src = f (dst + 0.5) - 0.5
+ *   rounded half away from zero; restated, not pinned against an installed skimage), crop [top, top + out_h) x
+ *   [left, left + out_w), class = the nearest of classes_dict["flood"] (0 cannot [255,0,0], 1 must [0,0,255], 2 may
+ *   [0,0,0]) by exact integer squared distance, first index on ties.  labels: uint8 [n][out_h][out_w].
+ * masker_eval: pred [n][h][w] of dtype CGAN_F16 / CGAN_BF16 / CGAN_F32 / CGAN_MEVAL_U8 (bool or uint8) / CGAN_MEVAL_F64,
+ *   labels uint8 [n][h][w] (0 cannot, 1 must, 2 may, anything else no class).  binarize = 1: pred := (pred > threshold)
+ *   before everything (eval_masker.py:507-508); 0: soft sums, and the edge map uses pred > edge_threshold
+ *   (edges_coherence_std_min's bin_th).  The caller rounds both thresholds to the comparison type.
+ *   pred_edge / label_edge: uint8 [n][h][w] edge masks of skimage 0.18.3 sobel (outer row / column zeroed) applied to the
+ *   binarised prediction and to (label == must).  maps (may be NULL): fp64 [6][n][h][w] = tp tn fp fn may_pos may_neg;
+ *   sobel (may be NULL): fp64 [2][n][h][w] = the two Sobel magnitude maps.
+ *   res: [n][16] 8-byte slots: int64 0..7 = #cannot #must #may, sum(pred) on cannot / must / may (integer predictions),
+ *   #prediction-edge and #label-edge pixels; fp64 8..13 = sum pred [must], sum (1 - pred) [cannot], sum pred [cannot],
+ *   sum (1 - pred) [must], sum pred [may], sum (1 - pred) [may]; fp64 14, 15 = mean and population std over the
+ *   prediction-edge pixels of sqrt(d2) / h, d2 = the exact integer squared distance to the nearest label-edge pixel
+ *   (1.0, 1.0 without a prediction edge; nan, nan with prediction edges and no label edge).  Six launches, fixed-order
+ *   reductions, no atomics: bit-identical from run to run and independent of the other images of the batch.
+ *   h, w <= 16384; workspace cgan_masker_eval_workspace_bytes(n, h, w). */
+#define CGAN_MEVAL_U8 3
+#define CGAN_MEVAL_F64 4
+int cgan_mask_label_encode(const void* img_hwc_u8, int32_t n, int32_t h, int32_t w, int32_t c, int32_t rows, int32_t cols,
+                           int32_t top, int32_t left, int32_t out_h, int32_t out_w, void* labels, void* stream);
+size_t cgan_masker_eval_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int cgan_masker_eval(const void* pred, int32_t pred_dtype, const void* labels, int32_t n, int32_t h, int32_t w,
+                     int32_t binarize, double threshold, double edge_threshold, void* pred_edge, void* label_edge,
+                     double* maps, double* sobel, int64_t* res, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange on RCCL.  The reference trains in ONE process on one device
  * (trainer.py:674-683: backward, then the optimizer on the local gradients); data parallelism over per-GPU slices needs the
