@@ -57,6 +57,21 @@ class AdamItem(C.Structure):
                 ("numel", C.c_int64)]
 
 
+class DataTfMap(C.Structure):
+    _fields_ = [("row_off", C.c_int32), ("col_off", C.c_int32), ("flip", C.c_int32)]
+
+
+class DataTfStage(C.Structure):
+    _fields_ = [("in_h", C.c_int32), ("in_w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32)]
+
+
+class DataTfItem(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_h", C.c_int32), ("src_w", C.c_int32),
+                ("channels", C.c_int32), ("stride_c", C.c_int32), ("stride_h", C.c_int32), ("stride_w", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("n_stages", C.c_int32), ("u8_min", C.c_float),
+                ("u8_range", C.c_float), ("stage", DataTfStage * 2), ("map", DataTfMap * 3)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -184,6 +199,8 @@ _SIGNATURES = {
                                                  C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "cgan_painter_heads_diffaug_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "cgan_data_transform": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
+    "cgan_data_jitter": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "cgan_avgpool3x3s2_bwd_nhwc": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "cgan_maxpool2x2_nhwc": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "cgan_maxpool2x2_bwd_nhwc": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

@@ -1,0 +1,372 @@
+// Training-data transforms (reference climategan/transforms.py:22-289, 424-490): the loaders' hflip / resize / crop / resize
+// pipeline, Normalize and BucketizeDepth as ONE gather per task and batch, and the pipeline's colour jitter.
+//   cgan_data_transform   sample k: source map of its own size -> dense [C][out_h][out_w] at its own dst.  The host reduces any
+//                         sequence of flips, crops and resizes to at most two resampling stages with an integer index map
+//                         before, between and after them (include/climategan_hip.h); the kernel walks that plan backwards
+//                         from the output pixel and touches only the source pixels the final window needs.
+//   cgan_data_jitter      brightness / saturation / contrast of the final-size x (transforms.py:494-541, the
+//                         is_diff_augment=False branches, bound to torchvision's documented formulas), the dummy pixels and,
+//                         on the last item, Normalize.
+// The index arithmetic is ATen's own, in fp32 (ATen/native/UpSample.h):
+//   nearest   nearest_idx -> nearest_neighbor_compute_source_index: min((int64)floorf(dst * scale), in - 1) with
+//             scale = compute_scales_value = (float)in / out
+//   bilinear  area_pixel_compute_scale (align_corners): (float)(in - 1) / (out - 1), 0 when out == 1;
+//             area_pixel_compute_source_index (align_corners): scale * dst; guard_index_and_lambda: i0 = min((int64)floorf(src),
+//             in - 1), lambda = clamp(src - i0, 0, 1); i1 = min(i0 + 1, in - 1); weights 1 - lambda, lambda
+// so the weights equal the reference's bit for bit; float64 index arithmetic is off by 1e-4 on x.  No contraction anywhere
+// in this file: a fused multiply-add in `scale * dst` followed by `- i0` would change lambda.
+// Memory-bound gathers: 32-bit offsets inside a sample, every load of a thread issued before its first use (16 taps x C for
+// x, four pixels per thread for the one-tap maps), non-temporal stores (the output is written once and read by a later
+// launch at the earliest).  No atomics, no LDS outside the contrast reduction.
+#include "cgan_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kParts = CGAN_DIFFAUG_PARTS;
+
+struct Affine4 {
+  float mean[4], std[4];
+};
+
+__device__ __forceinline__ int map_col(const CganDataTfMap& m, int j) { return m.flip ? m.col_off - j : m.col_off + j; }
+
+__device__ __forceinline__ int near_idx(int dst, int in, int out) {
+  return nearest_src(dst, (float)in / (float)out, in);   // cgan_common.h: min((int)floorf(dst * scale), in - 1)
+}
+
+__device__ __forceinline__ void bil_axis(int dst, int in, int out, int& i0, int& i1, float& lam) {
+  const float scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
+  const float src = scale * (float)dst;
+  const int f = (int)floorf(src);
+  i0 = f < in - 1 ? f : in - 1;
+  lam = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
+  i1 = i0 + 1 < in - 1 ? i0 + 1 : in - 1;
+}
+
+// ATen's order (UpSampleKernel.cpp, Interpolate<2>): rows outside, columns inside
+__device__ __forceinline__ float bil4(float ly, float lx, float v00, float v01, float v10, float v11) {
+  const float wy0 = 1.f - ly, wx0 = 1.f - lx;
+  return wy0 * (wx0 * v00 + lx * v01) + ly * (wx0 * v10 + lx * v11);
+}
+
+// ------------------------------------------------------------------------------------------------ nearest
+// source element offset of output pixel (oy, ox)
+template <int NS>
+__device__ __forceinline__ int near_offset(const CganDataTfItem& it, int oy, int ox) {
+  int y = it.map[NS].row_off + oy, x = map_col(it.map[NS], ox);
+#pragma unroll
+  for (int k = NS - 1; k >= 0; --k) {
+    y = it.map[k].row_off + near_idx(y, it.stage[k].in_h, it.stage[k].out_h);
+    x = map_col(it.map[k], near_idx(x, it.stage[k].in_w, it.stage[k].out_w));
+  }
+  return y * it.stride_h + x * it.stride_w;
+}
+
+// torch.bucketize(v, boundaries, right=True): the first index whose boundary is greater than v (ATen Bucketization.cpp,
+// cus_upper_bound: the same loop, so that a NaN lands where ATen puts it)
+__device__ __forceinline__ int bucket_of(float v, const float* __restrict__ b, int n) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (!(b[mid] > v)) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+constexpr int kNearPix = 4;   // output pixels per thread: that many loads in flight
+
+template <typename E, int NS, bool BUCKET>
+__global__ __launch_bounds__(256) void data_tf_nearest_kernel(const CganDataTfItem* __restrict__ items,
+                                                              const float* __restrict__ bounds, int n_bounds) {
+  const CganDataTfItem it = items[blockIdx.y];
+  const int ohw = it.out_h * it.out_w;
+  const int p0 = blockIdx.x * (256 * kNearPix) + threadIdx.x;
+  if (p0 >= ohw) return;
+  const E* src = reinterpret_cast<const E*>(it.src);
+  int off[kNearPix];
+#pragma unroll
+  for (int k = 0; k < kNearPix; ++k) {
+    const int p = p0 + k * 256;
+    const int pc = p < ohw ? p : p0;          // a thread past the end repeats its first pixel and does not store
+    const int oy = pc / it.out_w, ox = pc - oy * it.out_w;
+    off[k] = near_offset<NS>(it, oy, ox);
+  }
+  for (int c = 0; c < it.channels; ++c) {
+    E v[kNearPix];
+#pragma unroll
+    for (int k = 0; k < kNearPix; ++k) v[k] = src[c * it.stride_c + off[k]];
+#pragma unroll
+    for (int k = 0; k < kNearPix; ++k) {
+      const int p = p0 + k * 256;
+      if (p >= ohw) continue;
+      if constexpr (BUCKET) {
+        const int32_t b = bucket_of(__builtin_bit_cast(float, v[k]), bounds, n_bounds);
+        CGAN_ST_STREAM(b, reinterpret_cast<int32_t*>(it.dst) + c * ohw + p);
+      } else {
+        CGAN_ST_STREAM(v[k], reinterpret_cast<E*>(it.dst) + c * ohw + p);
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ bilinear
+template <bool U8>
+__device__ __forceinline__ float load_px(const void* src, int off, float mn, float rng) {
+  if constexpr (U8) return ((float)reinterpret_cast<const uint8_t*>(src)[off] - mn) / rng;   // data.py:386-387
+  else return reinterpret_cast<const float*>(src)[off];
+}
+
+template <bool U8, int NS, bool NORM>
+__global__ __launch_bounds__(256) void data_tf_bilinear_kernel(const CganDataTfItem* __restrict__ items, Affine4 aff) {
+  const CganDataTfItem it = items[blockIdx.y];
+  const int ohw = it.out_h * it.out_w;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= ohw) return;
+  const int oy = p / it.out_w, ox = p - oy * it.out_w;
+  const int y = it.map[NS].row_off + oy, x = map_col(it.map[NS], ox);
+  float* dst = reinterpret_cast<float*>(it.dst) + p;
+
+  // row and column offsets of the taps in the source, and the weights, from the output pixel down
+  constexpr int T = NS == 0 ? 1 : (NS == 1 ? 2 : 4);
+  int ro[T], co[T];
+  float LY = 0.f, LX = 0.f, ly[2] = {0.f, 0.f}, lx[2] = {0.f, 0.f};
+  if constexpr (NS == 0) {
+    ro[0] = y * it.stride_h;
+    co[0] = x * it.stride_w;
+  } else if constexpr (NS == 1) {
+    int a0, a1;
+    bil_axis(y, it.stage[0].in_h, it.stage[0].out_h, a0, a1, ly[0]);
+    ro[0] = (it.map[0].row_off + a0) * it.stride_h;
+    ro[1] = (it.map[0].row_off + a1) * it.stride_h;
+    bil_axis(x, it.stage[0].in_w, it.stage[0].out_w, a0, a1, lx[0]);
+    co[0] = map_col(it.map[0], a0) * it.stride_w;
+    co[1] = map_col(it.map[0], a1) * it.stride_w;
+  } else {
+    int Y[2], X[2];
+    bil_axis(y, it.stage[1].in_h, it.stage[1].out_h, Y[0], Y[1], LY);
+    bil_axis(x, it.stage[1].in_w, it.stage[1].out_w, X[0], X[1], LX);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      int a0, a1;
+      bil_axis(it.map[1].row_off + Y[a], it.stage[0].in_h, it.stage[0].out_h, a0, a1, ly[a]);
+      ro[2 * a] = (it.map[0].row_off + a0) * it.stride_h;
+      ro[2 * a + 1] = (it.map[0].row_off + a1) * it.stride_h;
+      bil_axis(map_col(it.map[1], X[a]), it.stage[0].in_w, it.stage[0].out_w, a0, a1, lx[a]);
+      co[2 * a] = map_col(it.map[0], a0) * it.stride_w;
+      co[2 * a + 1] = map_col(it.map[0], a1) * it.stride_w;
+    }
+  }
+  for (int c = 0; c < it.channels; ++c) {
+    const int cb = c * it.stride_c;
+    float t[T][T];
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+      for (int j = 0; j < T; ++j) t[i][j] = load_px<U8>(it.src, cb + ro[i] + co[j], it.u8_min, it.u8_range);
+    float v;
+    if constexpr (NS == 0) {
+      v = t[0][0];
+    } else if constexpr (NS == 1) {
+      v = bil4(ly[0], lx[0], t[0][0], t[0][1], t[1][0], t[1][1]);
+    } else {
+      // the four stage-1 pixels the second resampling reads, each a bilinear sample of the source
+      float s[2][2];
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+          s[a][b] = bil4(ly[a], lx[b], t[2 * a][2 * b], t[2 * a][2 * b + 1], t[2 * a + 1][2 * b], t[2 * a + 1][2 * b + 1]);
+      v = bil4(LY, LX, s[0][0], s[0][1], s[1][0], s[1][1]);
+    }
+    if constexpr (NORM) v = (v - aff.mean[c & 3]) / aff.std[c & 3];   // Normalize, transforms.py:214-237
+    CGAN_ST_STREAM(v, dst + c * ohw);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ colour jitter
+__device__ __forceinline__ float gray_of(float r, float g, float b) { return 0.2989f * r + 0.587f * g + 0.114f * b; }
+__device__ __forceinline__ float blend(float a, float b, float f, float omf) {
+  return fminf(fmaxf(f * a + omf * b, 0.f), 1.f);
+}
+
+__device__ inline float block_sum256(float v, float* sh) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  const float r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+// pass 1 of the contrast item: `parts` fixed-range partial sums of gray per image (the pattern of diffaug.hip)
+__global__ __launch_bounds__(256) void jitter_gray_sum_kernel(const float* __restrict__ x, float* __restrict__ ws, int hw,
+                                                              int parts) {
+  __shared__ float sh[256];
+  const float* xi = x + (long)blockIdx.y * 3 * hw;
+  const int chunk = (hw + parts - 1) / parts;
+  const int lo = blockIdx.x * chunk, hi = lo + chunk < hw ? lo + chunk : hw;
+  float s = 0.f;
+  for (int k = lo + threadIdx.x; k < hi; k += 256) s += gray_of(xi[k], xi[hw + k], xi[2 * hw + k]);
+  s = block_sum256(s, sh);
+  if (threadIdx.x == 0) ws[(long)blockIdx.y * kParts + blockIdx.x] = s;
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(256) void jitter_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                     const float* __restrict__ factors, int op, int hw,
+                                                     const float* __restrict__ ws, int parts, Affine4 aff) {
+  __shared__ float sh[256];
+  const int n = blockIdx.y;
+  const float f = factors[2 * n], omf = factors[2 * n + 1];
+  float mean = 0.f;
+  if (op == CGAN_JIT_CONTRAST)
+    mean = block_sum256((int)threadIdx.x < parts ? ws[(long)n * kParts + threadIdx.x] : 0.f, sh) / (float)hw;
+  const float* xi = x + (long)n * 3 * hw;
+  float* yi = y + (long)n * 3 * hw;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < hw; p += gridDim.x * 256) {
+    float v[3] = {CGAN_LD_STREAM(xi + p), CGAN_LD_STREAM(xi + hw + p), CGAN_LD_STREAM(xi + 2 * hw + p)};
+    const float other = op == CGAN_JIT_BRIGHTNESS ? 0.f : (op == CGAN_JIT_SATURATION ? gray_of(v[0], v[1], v[2]) : mean);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float o = blend(v[c], other, f, omf);
+      // "dummy pixels to fool scaling and preserve range" (transforms.py:504-506): [0, 0] = 1, then [-1, -1] = 0
+      if (p == 0) o = 1.f;
+      if (p == hw - 1) o = 0.f;
+      if constexpr (NORM) o = (o - aff.mean[c]) / aff.std[c];
+      CGAN_ST_STREAM(o, yi + c * hw + p);
+    }
+  }
+}
+
+bool window_inside(const CganDataTfMap& m, int wh, int ww, int H, int W) {
+  if (m.row_off < 0 || (long)m.row_off + wh > H) return false;
+  if (m.flip) return m.col_off <= W - 1 && (long)m.col_off - (ww - 1) >= 0;
+  return m.col_off >= 0 && (long)m.col_off + ww <= W;
+}
+
+}  // namespace
+
+extern "C" int cgan_data_transform(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count,
+                                   int32_t mode, int32_t src_kind, int32_t epilogue, const float* mean, const float* std,
+                                   const float* boundaries, int32_t n_boundaries, void* stream) {
+  CGAN_REQUIRE(items_host && items_device && count > 0 && count <= 65535, "data_transform: bad item table");
+  CGAN_REQUIRE(mode == CGAN_DTF_NEAREST || mode == CGAN_DTF_BILINEAR, "data_transform: bad mode %d", mode);
+  CGAN_REQUIRE(src_kind == CGAN_DTF_SRC_B4 || src_kind == CGAN_DTF_SRC_B8 || src_kind == CGAN_DTF_SRC_U8,
+               "data_transform: bad source kind %d", src_kind);
+  CGAN_REQUIRE(epilogue == CGAN_DTF_EPI_NONE || epilogue == CGAN_DTF_EPI_NORMALIZE || epilogue == CGAN_DTF_EPI_BUCKETIZE,
+               "data_transform: bad epilogue %d", epilogue);
+  if (mode == CGAN_DTF_BILINEAR) {
+    CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_B8, "data_transform: bilinear reads fp32 or uint8 sources");
+    CGAN_REQUIRE(epilogue != CGAN_DTF_EPI_BUCKETIZE, "data_transform: bucketize belongs to the nearest mode");
+    CGAN_REQUIRE(epilogue != CGAN_DTF_EPI_NORMALIZE || (mean && std), "data_transform: normalize needs mean and std");
+  } else {
+    CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_U8, "data_transform: uint8 sources are read by the bilinear mode only");
+    CGAN_REQUIRE(epilogue != CGAN_DTF_EPI_NORMALIZE, "data_transform: normalize belongs to the bilinear mode");
+    CGAN_REQUIRE(epilogue != CGAN_DTF_EPI_BUCKETIZE || (src_kind == CGAN_DTF_SRC_B4 && boundaries && n_boundaries > 0),
+                 "data_transform: bucketize needs fp32 sources and a boundaries array");
+  }
+  const int ns = items_host[0].n_stages;
+  CGAN_REQUIRE(ns >= 0 && ns <= 2, "data_transform: a plan has 0 to 2 resampling stages, got %d", ns);
+  long max_pix = 0;
+  for (int k = 0; k < count; ++k) {
+    const CganDataTfItem& it = items_host[k];
+    CGAN_REQUIRE(it.src && it.dst, "data_transform: item %d: null pointer", k);
+    CGAN_REQUIRE(it.n_stages == ns, "data_transform: item %d has %d stages, item 0 has %d", k, it.n_stages, ns);
+    CGAN_REQUIRE(it.src_h > 0 && it.src_w > 0 && it.channels > 0 && it.out_h > 0 && it.out_w > 0,
+                 "data_transform: item %d: bad shape", k);
+    CGAN_REQUIRE(epilogue != CGAN_DTF_EPI_NORMALIZE || it.channels <= 4, "data_transform: normalize takes at most 4 channels");
+    CGAN_REQUIRE(it.stride_c >= 0 && it.stride_h >= 0 && it.stride_w >= 0 &&
+                     (long)(it.channels - 1) * it.stride_c + (long)(it.src_h - 1) * it.stride_h +
+                             (long)(it.src_w - 1) * it.stride_w < (1l << 31),
+                 "data_transform: item %d: source strides outside 32-bit offsets", k);
+    CGAN_REQUIRE((long)it.channels * it.out_h * it.out_w < (1l << 31), "data_transform: item %d: output too large", k);
+    CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_U8 || it.u8_range != 0.f, "data_transform: item %d: zero uint8 range", k);
+    // every window inside the image below it: the sampled indices are clamped to the window, so nothing leaves the source
+    int wh = it.out_h, ww = it.out_w;
+    for (int s = ns; s >= 0; --s) {
+      int H = it.src_h, W = it.src_w;
+      if (s > 0) {
+        const CganDataTfStage& st = it.stage[s - 1];
+        CGAN_REQUIRE(st.in_h > 0 && st.in_w > 0 && st.out_h > 0 && st.out_w > 0, "data_transform: item %d: bad stage", k);
+        H = st.out_h, W = st.out_w;
+      }
+      CGAN_REQUIRE(window_inside(it.map[s], wh, ww, H, W),
+                   "data_transform: item %d: window %d x %d of map %d leaves its %d x %d image", k, wh, ww, s, H, W);
+      if (s > 0) wh = it.stage[s - 1].in_h, ww = it.stage[s - 1].in_w;
+    }
+    const long pix = (long)it.out_h * it.out_w;
+    max_pix = pix > max_pix ? pix : max_pix;
+  }
+  Affine4 aff = {{0.f, 0.f, 0.f, 0.f}, {1.f, 1.f, 1.f, 1.f}};
+  if (epilogue == CGAN_DTF_EPI_NORMALIZE)
+    for (int c = 0; c < 4; ++c) {
+      CGAN_REQUIRE(std[c] != 0.f, "data_transform: std[%d] is zero", c);
+      aff.mean[c] = mean[c], aff.std[c] = std[c];
+    }
+  hipStream_t s = (hipStream_t)stream;
+  if (mode == CGAN_DTF_NEAREST) {
+    const dim3 grid((unsigned)((max_pix + 256 * kNearPix - 1) / (256 * kNearPix)), count);
+#define NEAR(E, NS, B) \
+  hipLaunchKernelGGL((data_tf_nearest_kernel<E, NS, B>), grid, dim3(256), 0, s, items_device, boundaries, n_boundaries)
+#define NEAR_NS(E, B) \
+  do { if (ns == 0) NEAR(E, 0, B); else if (ns == 1) NEAR(E, 1, B); else NEAR(E, 2, B); } while (0)
+    if (epilogue == CGAN_DTF_EPI_BUCKETIZE) NEAR_NS(uint32_t, true);
+    else if (src_kind == CGAN_DTF_SRC_B8) NEAR_NS(uint64_t, false);
+    else NEAR_NS(uint32_t, false);
+#undef NEAR_NS
+#undef NEAR
+  } else {
+    const dim3 grid((unsigned)((max_pix + 255) / 256), count);
+#define BIL(U, NS, N) hipLaunchKernelGGL((data_tf_bilinear_kernel<U, NS, N>), grid, dim3(256), 0, s, items_device, aff)
+#define BIL_NS(U, N) \
+  do { if (ns == 0) BIL(U, 0, N); else if (ns == 1) BIL(U, 1, N); else BIL(U, 2, N); } while (0)
+    const bool norm = epilogue == CGAN_DTF_EPI_NORMALIZE;
+    if (src_kind == CGAN_DTF_SRC_U8) {
+      if (norm) BIL_NS(true, true); else BIL_NS(true, false);
+    } else {
+      if (norm) BIL_NS(false, true); else BIL_NS(false, false);
+    }
+#undef BIL_NS
+#undef BIL
+  }
+  CGAN_CHECK_LAUNCH("data_transform");
+  return CGAN_OK;
+}
+
+extern "C" int cgan_data_jitter(const float* x, float* y, const float* factors, int32_t op, int32_t n, int32_t h, int32_t w,
+                                const float* mean, const float* std, float* ws, void* stream) {
+  CGAN_REQUIRE(x && y && factors && x != y, "data_jitter: null or aliased pointer");
+  CGAN_REQUIRE(op == CGAN_JIT_BRIGHTNESS || op == CGAN_JIT_SATURATION || op == CGAN_JIT_CONTRAST, "data_jitter: bad op %d", op);
+  CGAN_REQUIRE(n > 0 && n <= 65535 && h > 0 && w > 0 && (long)h * w * 3 < (1l << 31), "data_jitter: bad shape");
+  CGAN_REQUIRE(op != CGAN_JIT_CONTRAST || ws, "data_jitter: contrast needs a workspace");
+  CGAN_REQUIRE((mean == nullptr) == (std == nullptr), "data_jitter: mean and std come together");
+  const int hw = h * w;
+  long p = ((long)hw + 4095) / 4096;
+  const int parts = (int)(p < 1 ? 1 : (p > kParts ? kParts : p));
+  hipStream_t s = (hipStream_t)stream;
+  if (op == CGAN_JIT_CONTRAST) {
+    hipLaunchKernelGGL(jitter_gray_sum_kernel, dim3(parts, n), dim3(256), 0, s, x, ws, hw, parts);
+    CGAN_CHECK_LAUNCH("data_jitter_sum");
+  }
+  long blocks = ((long)hw + 255) / 256, cap = 16384 / n;
+  if (cap < 4) cap = 4;
+  const dim3 grid((unsigned)(blocks < cap ? blocks : cap), n);
+  Affine4 aff = {{0.f, 0.f, 0.f, 0.f}, {1.f, 1.f, 1.f, 1.f}};
+  if (mean) {
+    for (int c = 0; c < 3; ++c) {
+      CGAN_REQUIRE(std[c] != 0.f, "data_jitter: std[%d] is zero", c);
+      aff.mean[c] = mean[c], aff.std[c] = std[c];
+    }
+    hipLaunchKernelGGL(jitter_kernel<true>, grid, dim3(256), 0, s, x, y, factors, op, hw, (const float*)ws, parts, aff);
+  } else {
+    hipLaunchKernelGGL(jitter_kernel<false>, grid, dim3(256), 0, s, x, y, factors, op, hw, (const float*)ws, parts, aff);
+  }
+  CGAN_CHECK_LAUNCH("data_jitter");
+  return CGAN_OK;
+}

@@ -1598,6 +1598,147 @@ def painter_heads_diffaug_bwd(d_d_in: NHWC, d_vgg_in: Optional[NHWC], m: torch.T
     return NHWC(dfake, 3)
 
 
+# ---- training-data transforms (csrc/data_tf.hip) ---------------------------------------------------------------------
+DTF_NEAREST, DTF_BILINEAR = 0, 1
+DTF_EPI_NONE, DTF_EPI_NORMALIZE, DTF_EPI_BUCKETIZE = 0, 1, 2
+JIT_BRIGHTNESS, JIT_SATURATION, JIT_CONTRAST = 1, 2, 3
+
+
+def _f4(values):
+    v = [float(a) for a in values]
+    return (C.c_float * 4)(*(v + [v[-1]] * (4 - len(v))))
+
+
+def _i32(what, *values):
+    """The descriptor's fields are int32 and ctypes truncates silently: refuse what does not fit"""
+    for v in values:
+        if not -2 ** 31 <= int(v) < 2 ** 31:
+            raise RuntimeError("data_transform: %s %d does not fit the descriptor's 32-bit fields" % (what, int(v)))
+    return [int(v) for v in values]
+
+
+def data_transform(sources, plans, mode: int, normalize=None, boundaries: Optional[torch.Tensor] = None, u8_ranges=None,
+                   dense=True):
+    """One launch: sample k's source map through its plan into its own [C, h, w] map (cgan_data_transform).
+
+    ``sources``: device tensors, [1, C, H, W] or [C, H, W] with any strides (views are read in place), all fp32, all int32 or
+    all int64; or, with ``u8_ranges`` = [(min, max - min), ...], uint8 [H, W, C] images (bilinear only).  ``plans``: per
+    sample ``(stages, maps, (out_h, out_w))`` with ``stages`` up to two ``(in_h, in_w, out_h, out_w)`` and ``maps`` =
+    len(stages) + 1 triples ``(row_off, col_off, flip)`` (include/climategan_hip.h).  ``normalize`` = (mean, std) per channel
+    (bilinear), ``boundaries`` = the fp32 device tensor of torch.bucketize's boundaries (nearest, fp32 in, int32 out).
+    Returns the dense [N, C, h, w] batch, or with ``dense=False`` a list of [1, C, h_k, w_k] maps (sizes may differ)."""
+    _need_cuda(*sources, boundaries)
+    n = len(sources)
+    if n == 0 or len(plans) != n:
+        raise RuntimeError("data_transform: %d sources, %d plans" % (n, len(plans)))
+    dt = sources[0].dtype
+    if any(t.dtype != dt or t.device != sources[0].device for t in sources):
+        raise RuntimeError("data_transform: the sources of one launch share dtype and device")
+    u8 = u8_ranges is not None
+    if u8:
+        if dt != torch.uint8 or mode != DTF_BILINEAR or any(t.dim() != 3 for t in sources):
+            raise RuntimeError("data_transform: u8_ranges go with uint8 [H, W, C] sources in the bilinear mode")
+        kind = 2
+    elif dt in (torch.float32, torch.int32):
+        kind = 0
+    elif dt == torch.int64:
+        kind = 1
+    else:
+        raise RuntimeError("data_transform: sources must be float32, int32, int64 or (with u8_ranges) uint8, got %s" % dt)
+    if (mode == DTF_BILINEAR or boundaries is not None) and not u8 and dt != torch.float32:
+        raise RuntimeError("data_transform: the bilinear mode and bucketize read float32 maps, got %s" % dt)
+    epi = DTF_EPI_NONE
+    mean = std = None
+    if normalize is not None:
+        epi, mean, std = DTF_EPI_NORMALIZE, _f4(normalize[0]), _f4(normalize[1])
+    if boundaries is not None:
+        if boundaries.dtype != torch.float32 or boundaries.dim() != 1 or not boundaries.is_contiguous():
+            raise RuntimeError("data_transform: boundaries must be a contiguous 1-D float32 tensor")
+        epi = DTF_EPI_BUCKETIZE
+    out_dt = torch.int32 if boundaries is not None else (torch.float32 if mode == DTF_BILINEAR else dt)
+    items = (_lib.DataTfItem * n)()
+    shapes, total = [], 0
+    for k, (t, (stages, maps, (oh, ow))) in enumerate(zip(sources, plans)):
+        if u8:
+            (h, w, c), (sh, sw, sc) = t.shape, t.stride()
+        else:
+            if t.dim() == 4:
+                if t.shape[0] != 1:
+                    raise RuntimeError("data_transform: a source is one sample ([1, C, H, W]), got %s" % (tuple(t.shape),))
+                t = t[0]
+            if t.dim() != 3:
+                raise RuntimeError("data_transform: a source is [1, C, H, W] or [C, H, W], got %s" % (tuple(t.shape),))
+            (c, h, w), (sc, sh, sw) = t.shape, t.stride()
+        if len(stages) > 2 or len(maps) != len(stages) + 1:
+            raise RuntimeError("data_transform: a plan has at most two stages and one map more than stages")
+        it = items[k]
+        it.src = t.data_ptr()
+        it.src_h, it.src_w, it.channels = _i32("source size", h, w, c)
+        it.stride_c, it.stride_h, it.stride_w = _i32("source stride", sc, sh, sw)
+        it.out_h, it.out_w = _i32("output size", oh, ow)
+        it.n_stages = len(stages)
+        if u8:
+            it.u8_min, it.u8_range = float(u8_ranges[k][0]), float(u8_ranges[k][1])
+        for i, st in enumerate(stages):
+            it.stage[i] = _lib.DataTfStage(*_i32("stage size", *st))
+        for i, m in enumerate(maps):
+            it.map[i] = _lib.DataTfMap(*_i32("map offset", m[0], m[1]), int(bool(m[2])))
+        shapes.append((c, oh, ow))
+        total += c * oh * ow
+        if _lib.CALL_LOG is not None:
+            _lib.log_bytes(c * oh * ow * (t.element_size() + torch.empty(0, dtype=out_dt).element_size()))
+    if dense and any(sh != shapes[0] for sh in shapes):
+        raise RuntimeError("data_transform: a dense batch needs one output shape, got %s" % sorted(set(shapes)))
+    dev = sources[0].device
+    flat = torch.empty(total, dtype=out_dt, device=dev)
+    if flat.nbytes >= ABI_MAX_BYTES:
+        raise RuntimeError("data_transform: %.2f GiB of output in one call; use a smaller batch" % (flat.nbytes / 2 ** 30))
+    off = 0
+    for k, (c, oh, ow) in enumerate(shapes):
+        items[k].dst = flat.data_ptr() + off * flat.element_size()
+        off += c * oh * ow
+    # pinned + non_blocking, like the optimizer's item table: the host does not wait for the stream.  Neither buffer needs
+    # to be kept: the copy and the launch go on the current stream and torch's caching allocators are stream-ordered (a
+    # pinned block is not handed out again before the copy that read it has run, a device block not before the work queued
+    # on its stream)
+    host = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).pin_memory()
+    table = host.to(dev, non_blocking=True)
+    _lib.check(_lib.load().cgan_data_transform(C.cast(items, C.c_void_p), C.c_void_p(table.data_ptr()), n, int(mode), kind, epi,
+                                               C.cast(mean, C.c_void_p) if mean is not None else None,
+                                               C.cast(std, C.c_void_p) if std is not None else None,
+                                               _ptr(boundaries), 0 if boundaries is None else boundaries.numel(), _stream()),
+               "cgan_data_transform")
+    if dense:
+        return flat.view(n, *shapes[0])
+    outs, off = [], 0
+    for c, oh, ow in shapes:
+        outs.append(flat[off:off + c * oh * ow].view(1, c, oh, ow))
+        off += c * oh * ow
+    return outs
+
+
+def data_jitter(x: torch.Tensor, op: int, factors: torch.Tensor, normalize=None) -> torch.Tensor:
+    """One colour-jitter item of the data pipeline on an [N, 3, H, W] fp32 batch in [0, 1] (cgan_data_jitter): the blend,
+    the two dummy pixels and, with ``normalize`` = (mean, std), Normalize.  ``factors``: [N, 2] fp32 = (f, 1 - f)."""
+    _need_cuda(x, factors)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("data_jitter: x must be an [N, 3, H, W] float32 tensor, got %s %s" % (tuple(x.shape), x.dtype))
+    n, _, h, w = x.shape
+    if factors.dtype != torch.float32 or tuple(factors.shape) != (n, 2) or not factors.is_contiguous():
+        raise RuntimeError("data_jitter: factors must be a contiguous [%d, 2] float32 tensor" % n)
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    ws = torch.empty((n, DIFFAUG_PARTS), dtype=torch.float32, device=x.device) if op == JIT_CONTRAST else None
+    mean = std = None
+    if normalize is not None:
+        mean, std = _f4(normalize[0]), _f4(normalize[1])
+    _lib.check(_lib.load().cgan_data_jitter(_ptr(x), _ptr(y), _ptr(factors), int(op), n, h, w,
+                                            C.cast(mean, C.c_void_p) if mean is not None else None,
+                                            C.cast(std, C.c_void_p) if std is not None else None, _ptr(ws), _stream()),
+               "cgan_data_jitter")
+    return y
+
+
 @_batch_chunked("dy", out_bytes_per_sample=lambda g: g("in_hw")[0] * g("in_hw")[1] * g("dy").cs * 2)
 def avgpool3x3s2_bwd(dy: NHWC, in_hw) -> NHWC:
     _need_cuda(dy.t)

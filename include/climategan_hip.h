@@ -801,6 +801,65 @@ int cgan_pair_mul(const void* a3, const void* b3, void* y3, int32_t dtype, int64
 int cgan_pair_copy_channels(const void* src3, void* dst3, int32_t dtype, int64_t npix, int32_t c, int32_t c_dst, int32_t c_off,
                             void* stream);
 
+/* ---- training-data transforms (csrc/data_tf.hip; reference climategan/transforms.py:22-289, 424-490) ----------------------
+ * data_transform: ONE launch transforms one task of a whole batch.  Sample k reads its own source map (any size, any
+ * element strides: a CHW tensor, a view of one, or an HWC image) and writes its own dense [channels][out_h][out_w] map at
+ * dst (the samples of a collated batch: dst = base + k * channels * out_h * out_w).  The plan of a sample is what any
+ * sequence of hflip / crop / resize items reduces to: up to two resampling stages and, before, between and after them, an
+ * integer index map -- window pixel (i, j) of map m is pixel (row_off + i, col_off + j) of the image below it, or
+ * (row_off + i, col_off - j) when flip is set.  map[0] lies on the source, map[k] on the output of stage k - 1, and the
+ * output is the window out_h x out_w of map[n_stages].
+ *   CGAN_DTF_NEAREST   src = min((int)floorf(dst * scale), in - 1), scale = (float)in / out: F.interpolate(mode="nearest").
+ *                      A pure gather of 4- or 8-byte elements (fp32, int32, int64); with CGAN_DTF_EPI_BUCKETIZE the fp32
+ *                      value v becomes the int32 index of torch.bucketize(v, boundaries, right=True).
+ *   CGAN_DTF_BILINEAR  F.interpolate(mode="bilinear", align_corners=True) in its own fp32 index arithmetic (scale =
+ *                      (float)(in - 1) / (out - 1), src = scale * dst, lambda = src - (int)src); two stages = a bilinear
+ *                      sample of bilinear samples, 16 taps.  Sources: fp32, or uint8 read as ((float)v - u8_min) / u8_range
+ *                      (tensor_loader's arr -= arr.min(); arr /= arr.max(), data.py:385-387).  fp32 out; with
+ *                      CGAN_DTF_EPI_NORMALIZE (v - mean[c]) / std[c] (channels <= 4).
+ * mean / std: host arrays of 4 floats; boundaries: device.  items_host is the table the call validates (every index of every plan inside its image) and sizes the grid from;
+ * items_device is the same table in device memory, which the kernel reads.
+ * data_jitter: one colour-jitter item of the data pipeline on an NCHW fp32 batch of 3-channel images in [0, 1]
+ * (transforms.py:494-541, is_diff_augment=False, bound to torchvision's documented formulas): gray = 0.2989 r + 0.587 g +
+ * 0.114 b, blend(a, b, f) = clamp(f a + (1 - f) b, 0, 1); brightness blend(x, 0, f), saturation blend(x, gray, f), contrast
+ * blend(x, mean(gray), f); then the dummy pixels y[:, :, 0, 0] = 1, y[:, :, -1, -1] = 0; then, with mean / std given,
+ * (y - mean[c]) / std[c] (host arrays of 4 floats, like data_transform's; NULL: none).  factors [n][2] fp32 (device): f and
+ * 1 - f, each rounded from the double the reference draws (torchvision forms 1.0 - ratio in a Python float).
+ * ws: CGAN_DIFFAUG_PARTS floats per image (contrast only: fixed-order partial sums, no atomics). */
+#define CGAN_DTF_NEAREST 0
+#define CGAN_DTF_BILINEAR 1
+#define CGAN_DTF_SRC_B4 0  /* 4-byte elements: fp32 (the only one bilinear and bucketize take), int32 */
+#define CGAN_DTF_SRC_B8 1  /* 8-byte elements: int64 */
+#define CGAN_DTF_SRC_U8 2  /* uint8, bilinear only */
+#define CGAN_DTF_EPI_NONE 0
+#define CGAN_DTF_EPI_NORMALIZE 1
+#define CGAN_DTF_EPI_BUCKETIZE 2
+#define CGAN_JIT_BRIGHTNESS 1
+#define CGAN_JIT_SATURATION 2
+#define CGAN_JIT_CONTRAST 3
+typedef struct {
+  int32_t row_off, col_off, flip;
+} CganDataTfMap;
+typedef struct {
+  int32_t in_h, in_w, out_h, out_w;
+} CganDataTfStage;
+typedef struct {
+  const void* src;
+  void* dst;
+  int32_t src_h, src_w, channels;
+  int32_t stride_c, stride_h, stride_w; /* of src, in elements */
+  int32_t out_h, out_w;
+  int32_t n_stages;
+  float u8_min, u8_range;
+  CganDataTfStage stage[2];
+  CganDataTfMap map[3];
+} CganDataTfItem;
+int cgan_data_transform(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count, int32_t mode,
+                        int32_t src_kind, int32_t epilogue, const float* mean, const float* std, const float* boundaries,
+                        int32_t n_boundaries, void* stream);
+int cgan_data_jitter(const float* x, float* y, const float* factors, int32_t op, int32_t n, int32_t h, int32_t w,
+                     const float* mean, const float* std, float* ws, void* stream);
+
 /* libcgan_hip.so exports exactly the entry points declared above: no development knob, no process-global mutable state
  * behind the ABI besides the thread-local error string and the lazily loaded RCCL handle.  The kernel-selection /
  * ablation / timestamp knobs (cgan_debug_set_*) that tools/ and the every-kernel-variant tests use exist only in the
