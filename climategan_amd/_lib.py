@@ -69,7 +69,17 @@ class DataTfItem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_h", C.c_int32), ("src_w", C.c_int32),
                 ("channels", C.c_int32), ("stride_c", C.c_int32), ("stride_h", C.c_int32), ("stride_w", C.c_int32),
                 ("out_h", C.c_int32), ("out_w", C.c_int32), ("n_stages", C.c_int32), ("u8_min", C.c_float),
-                ("u8_range", C.c_float), ("stage", DataTfStage * 2), ("map", DataTfMap * 3)]
+                ("u8_range", C.c_float), ("stage", DataTfStage * 2), ("map", DataTfMap * 3),
+                ("stats", C.c_void_p), ("far_plane", C.c_float), ("dec_flags", C.c_int32)]
+
+
+class DataTfPalette(C.Structure):
+    _fields_ = [("n", C.c_int32), ("default_class", C.c_int32), ("colour", C.c_uint32 * 16), ("cls", C.c_int32 * 16)]
+
+
+class DataMinmaxItem(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("out", C.c_void_p), ("pixels", C.c_int64), ("channels", C.c_int32),
+                ("far_plane", C.c_float)]
 
 
 _P = C.c_void_p
@@ -200,6 +210,8 @@ _SIGNATURES = {
     "cgan_painter_heads_diffaug_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "cgan_data_transform": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
+    "cgan_data_transform_raw": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P]),
+    "cgan_data_source_minmax": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "cgan_data_jitter": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "cgan_avgpool3x3s2_bwd_nhwc": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "cgan_maxpool2x2_nhwc": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

@@ -4,6 +4,12 @@
 //                         sequence of flips, crops and resizes to at most two resampling stages with an integer index map
 //                         before, between and after them (include/climategan_hip.h); the kernel walks that plan backwards
 //                         from the output pixel and touches only the source pixels the final window needs.
+//   cgan_data_transform_raw  the same with the raw source kinds of the nearest mode: tensor_loader's decode (data.py:91-148,
+//                         231-252, 344-399; tutils.py:195-293) applied to the gathered pixel before the store, so that a
+//                         160 x 160 task decodes 1 % of a 1200 x 1800 source and the upload is the file's own bytes.
+//   cgan_data_source_minmax  the one thing that has to see the whole source: min / max for the normalised depth modes, x and
+//                         the mask's "max > 127", as fixed-range partials over 16-byte non-temporal loads and a fixed-order
+//                         finish that leaves (min, range, max, flag) where the gather's items point.
 //   cgan_data_jitter      brightness / saturation / contrast of the final-size x (transforms.py:494-541, the
 //                         is_diff_augment=False branches, bound to torchvision's documented formulas), the dummy pixels and,
 //                         on the last item, Normalize.
@@ -112,6 +118,228 @@ __global__ __launch_bounds__(256) void data_tf_nearest_kernel(const CganDataTfIt
   }
 }
 
+// ------------------------------------------------------------------------------------------------ raw sources
+// The decode of one gathered pixel.  fp32 division, multiplication and reciprocal are the IEEE operations (contraction is off
+// and nothing here is built with fast-math); the integer parts are exact.
+__device__ __forceinline__ float unity_depth(int r, int g, int b, float far_plane) {
+  // tutils.py:276-280: ((247 - R) / 8).type(IntTensor) truncates toward zero like C's int division: 248..254 -> 0, 255 -> -1
+  const int code = ((247 - r) / 8) * (256 * 31) + ((247 - g) / 8) * 256 + (255 - b);
+  return (float)code / 246015.f * far_plane;
+}
+__device__ __forceinline__ float kitti_depth(uint32_t v) { return (float)v / 100.f; }   // tutils.py:208
+
+// log in float64 on the fp32 depth, rounded once more to fp32: correctly rounded up to double rounding
+__device__ __forceinline__ float log_f32(float d) { return (float)log((double)d); }
+
+// NaN wins, as in torch.min / torch.max
+__device__ __forceinline__ float nan_min(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
+__device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
+
+template <int KIND>
+__device__ __forceinline__ uint32_t load_raw(const void* src, int off, int sc) {
+  if constexpr (KIND == CGAN_DTF_SRC_KITTI_D) {
+    return reinterpret_cast<const uint16_t*>(src)[off];
+  } else if constexpr (KIND == CGAN_DTF_SRC_F32_D) {
+    return reinterpret_cast<const uint32_t*>(src)[off];
+  } else {
+    const uint8_t* p = reinterpret_cast<const uint8_t*>(src) + off;
+    uint32_t v = p[0];
+    if constexpr (KIND != CGAN_DTF_SRC_MASK) v |= (uint32_t)p[sc] << 8 | (uint32_t)p[2 * sc] << 16;
+    if constexpr (KIND == CGAN_DTF_SRC_SEG_NEAREST) v |= (uint32_t)p[3 * sc] << 24;
+    return v;
+  }
+}
+
+struct RawConsts {
+  float mn, rng, far_plane;
+  int flags;
+};
+
+template <int KIND>
+__device__ __forceinline__ float decode_raw(uint32_t raw, const RawConsts& k, const CganDataTfPalette& pal) {
+  if constexpr (KIND == CGAN_DTF_SRC_UNITY_D || KIND == CGAN_DTF_SRC_KITTI_D) {
+    const float depth = KIND == CGAN_DTF_SRC_UNITY_D
+                            ? unity_depth(raw & 255, (raw >> 8) & 255, (raw >> 16) & 255, k.far_plane)
+                            : kitti_depth(raw);
+    if (k.flags & CGAN_DTF_DEC_LOG) return log_f32(depth);
+    const float inv = 1.f / depth;
+    return (k.flags & CGAN_DTF_DEC_NORMALIZE) ? (inv - k.mn) / k.rng : inv;
+  } else if constexpr (KIND == CGAN_DTF_SRC_F32_D) {
+    return (__builtin_bit_cast(float, raw) - k.mn) / k.rng;               // tutils.py:199-201
+  } else if constexpr (KIND == CGAN_DTF_SRC_MASK) {
+    return (k.flags & CGAN_DTF_DEC_THRESHOLD) ? (raw > 127u ? 1.f : 0.f) : (float)raw;   // data.py:392-393
+  } else if constexpr (KIND == CGAN_DTF_SRC_SEG_EXACT) {
+    int cls = pal.default_class;                                          // data.py:104-107, 123-126
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (i < pal.n && raw == pal.colour[i]) cls = pal.cls[i];
+    return (float)cls;
+  } else {
+    int best = 0x7fffffff, cls = 0;                                       // data.py:221-228: strict <, the first wins
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      if (i < pal.n) {
+        const uint32_t c = pal.colour[i];
+        const int d0 = (int)(raw & 255) - (int)(c & 255), d1 = (int)((raw >> 8) & 255) - (int)((c >> 8) & 255);
+        const int d2 = (int)((raw >> 16) & 255) - (int)((c >> 16) & 255), d3 = (int)(raw >> 24) - (int)(c >> 24);
+        const int d = d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+        if (d < best) best = d, cls = pal.cls[i];
+      }
+    }
+    return (float)cls;
+  }
+}
+
+template <int KIND, int NS, bool BUCKET>
+__global__ __launch_bounds__(256) void data_tf_decode_kernel(const CganDataTfItem* __restrict__ items,
+                                                             const float* __restrict__ bounds, int n_bounds,
+                                                             CganDataTfPalette pal) {
+  const CganDataTfItem it = items[blockIdx.y];
+  const int ohw = it.out_h * it.out_w;
+  const int p0 = blockIdx.x * (256 * kNearPix) + threadIdx.x;
+  if (p0 >= ohw) return;
+  uint32_t raw[kNearPix];
+#pragma unroll
+  for (int k = 0; k < kNearPix; ++k) {
+    const int p = p0 + k * 256;
+    const int pc = p < ohw ? p : p0;
+    const int oy = pc / it.out_w, ox = pc - oy * it.out_w;
+    raw[k] = load_raw<KIND>(it.src, near_offset<NS>(it, oy, ox), it.stride_c);
+  }
+  RawConsts kc = {it.u8_min, it.u8_range, it.far_plane, it.dec_flags};
+  if (it.stats) {   // written by cgan_data_source_minmax earlier on this stream
+    kc.mn = it.stats[0], kc.rng = it.stats[1];
+    kc.flags = (kc.flags & ~CGAN_DTF_DEC_THRESHOLD) | (it.stats[3] != 0.f ? CGAN_DTF_DEC_THRESHOLD : 0);
+  }
+#pragma unroll
+  for (int k = 0; k < kNearPix; ++k) {
+    const int p = p0 + k * 256;
+    if (p >= ohw) continue;
+    const float v = decode_raw<KIND>(raw[k], kc, pal);
+    if constexpr (BUCKET) {
+      CGAN_ST_STREAM((int32_t)bucket_of(v, bounds, n_bounds), reinterpret_cast<int32_t*>(it.dst) + p);
+    } else if constexpr (KIND == CGAN_DTF_SRC_SEG_EXACT) {
+      CGAN_ST_STREAM((double)v, reinterpret_cast<double*>(it.dst) + p);   // torch.tensor(np.ones(...) * 14): float64
+    } else {
+      CGAN_ST_STREAM(v, reinterpret_cast<float*>(it.dst) + p);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ whole-source min / max
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// a group = 16 bytes of a one-value-per-element source, or 16 pixels (CH x 16 bytes) of a Unity depth code
+template <int KIND, int CH>
+struct MinmaxGroup {
+  static constexpr int kLoads = KIND == CGAN_DTF_SRC_UNITY_D ? CH : 1;
+  static constexpr int kUnits = KIND == CGAN_DTF_SRC_KITTI_D ? 8 : (KIND == CGAN_DTF_SRC_F32_D ? 4 : 16);
+  static constexpr int kUnitBytes = KIND == CGAN_DTF_SRC_UNITY_D ? CH : 16 / kUnits;
+};
+
+// number of units of a sample: pixels, or bytes for the kinds that look at every channel
+template <int KIND>
+__device__ __forceinline__ long minmax_units(const CganDataMinmaxItem& it) {
+  return (KIND == CGAN_DTF_SRC_U8 || KIND == CGAN_DTF_SRC_MASK) ? it.pixels * it.channels : it.pixels;
+}
+
+__host__ __device__ inline int minmax_parts(long groups) {
+  const long p = (groups + 1023) / 1024;   // about four groups per thread
+  return (int)(p < 1 ? 1 : (p > kParts ? kParts : p));
+}
+
+template <int KIND>
+__device__ __forceinline__ float minmax_value(uint32_t raw, float far_plane) {
+  if constexpr (KIND == CGAN_DTF_SRC_UNITY_D)
+    return 1.f / unity_depth(raw & 255, (raw >> 8) & 255, (raw >> 16) & 255, far_plane);
+  else if constexpr (KIND == CGAN_DTF_SRC_KITTI_D) return 1.f / kitti_depth(raw);
+  else if constexpr (KIND == CGAN_DTF_SRC_F32_D) return __builtin_bit_cast(float, raw);
+  else return (float)raw;
+}
+
+__device__ __forceinline__ uint32_t byte_of(const uint32_t* w, int k) { return (w[k >> 2] >> ((k & 3) * 8)) & 255u; }
+
+__device__ inline void block_minmax256(float& mn, float& mx, float* sh) {
+  sh[threadIdx.x] = mn, sh[256 + threadIdx.x] = mx;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      sh[threadIdx.x] = nan_min(sh[threadIdx.x], sh[threadIdx.x + s]);
+      sh[256 + threadIdx.x] = nan_max(sh[256 + threadIdx.x], sh[256 + threadIdx.x + s]);
+    }
+    __syncthreads();
+  }
+  mn = sh[0], mx = sh[256];
+}
+
+template <int KIND, int CH>
+__global__ __launch_bounds__(256) void minmax_partial_kernel(const CganDataMinmaxItem* __restrict__ items,
+                                                             float* __restrict__ ws) {
+  using G = MinmaxGroup<KIND, CH>;
+  __shared__ float sh[512];
+  const CganDataMinmaxItem it = items[blockIdx.y];
+  const long units = minmax_units<KIND>(it), groups = units / G::kUnits;
+  const int parts = minmax_parts(groups);
+  if ((int)blockIdx.x >= parts) return;
+  const long chunk = (groups + parts - 1) / parts;
+  const long lo = blockIdx.x * chunk, hi = lo + chunk < groups ? lo + chunk : groups;
+  float mn = __builtin_inff(), mx = -__builtin_inff();
+  const u32x4* src = reinterpret_cast<const u32x4*>(it.src);
+  for (long g = lo + threadIdx.x; g < hi; g += 256) {
+    uint32_t w[4 * G::kLoads];
+#pragma unroll
+    for (int j = 0; j < G::kLoads; ++j) {
+      const u32x4 q = CGAN_LD_STREAM(src + g * G::kLoads + j);
+      w[4 * j] = q.x, w[4 * j + 1] = q.y, w[4 * j + 2] = q.z, w[4 * j + 3] = q.w;
+    }
+#pragma unroll
+    for (int u = 0; u < G::kUnits; ++u) {
+      uint32_t raw;
+      if constexpr (KIND == CGAN_DTF_SRC_UNITY_D)
+        raw = byte_of(w, u * CH) | byte_of(w, u * CH + 1) << 8 | byte_of(w, u * CH + 2) << 16;
+      else if constexpr (KIND == CGAN_DTF_SRC_KITTI_D) raw = (w[u >> 1] >> ((u & 1) * 16)) & 0xffffu;
+      else if constexpr (KIND == CGAN_DTF_SRC_F32_D) raw = w[u];
+      else raw = byte_of(w, u);
+      const float v = minmax_value<KIND>(raw, it.far_plane);
+      mn = nan_min(mn, v), mx = nan_max(mx, v);
+    }
+  }
+  // the units behind the last whole group: fewer than 16, read one by one by the last part's first thread
+  if ((int)blockIdx.x == parts - 1 && threadIdx.x == 0) {
+    const uint8_t* b = reinterpret_cast<const uint8_t*>(it.src);
+    for (long u = groups * G::kUnits; u < units; ++u) {
+      const uint8_t* p = b + u * G::kUnitBytes;
+      uint32_t raw = p[0];
+      if constexpr (KIND == CGAN_DTF_SRC_UNITY_D) raw |= (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16;
+      else if constexpr (KIND == CGAN_DTF_SRC_KITTI_D) raw |= (uint32_t)p[1] << 8;
+      else if constexpr (KIND == CGAN_DTF_SRC_F32_D) raw |= (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+      const float v = minmax_value<KIND>(raw, it.far_plane);
+      mn = nan_min(mn, v), mx = nan_max(mx, v);
+    }
+  }
+  block_minmax256(mn, mx, sh);
+  if (threadIdx.x == 0) {
+    float* o = ws + ((long)blockIdx.y * kParts + blockIdx.x) * 2;
+    o[0] = mn, o[1] = mx;
+  }
+}
+
+template <int KIND, int CH>
+__global__ __launch_bounds__(256) void minmax_finish_kernel(const CganDataMinmaxItem* __restrict__ items,
+                                                            const float* __restrict__ ws) {
+  __shared__ float sh[512];
+  const CganDataMinmaxItem it = items[blockIdx.x];
+  const int parts = minmax_parts(minmax_units<KIND>(it) / MinmaxGroup<KIND, CH>::kUnits);
+  const float* p = ws + ((long)blockIdx.x * kParts + threadIdx.x) * 2;
+  const bool have = (int)threadIdx.x < parts;
+  float mn = have ? p[0] : __builtin_inff(), mx = have ? p[1] : -__builtin_inff();
+  block_minmax256(mn, mx, sh);
+  if (threadIdx.x == 0) {
+    it.out[0] = mn, it.out[1] = mx - mn;   // t = t - min(t); t = t / max(t): the divisor is max - min in fp32
+    it.out[2] = mx, it.out[3] = mx > 127.f ? 1.f : 0.f;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ bilinear
 template <bool U8>
 __device__ __forceinline__ float load_px(const void* src, int off, float mn, float rng) {
@@ -159,13 +387,15 @@ __global__ __launch_bounds__(256) void data_tf_bilinear_kernel(const CganDataTfI
       co[2 * a + 1] = map_col(it.map[0], a1) * it.stride_w;
     }
   }
+  // an x source whose min / max the host has not computed: cgan_data_source_minmax left them earlier on this stream
+  const float u8_min = U8 && it.stats ? it.stats[0] : it.u8_min, u8_range = U8 && it.stats ? it.stats[1] : it.u8_range;
   for (int c = 0; c < it.channels; ++c) {
     const int cb = c * it.stride_c;
     float t[T][T];
 #pragma unroll
     for (int i = 0; i < T; ++i)
 #pragma unroll
-      for (int j = 0; j < T; ++j) t[i][j] = load_px<U8>(it.src, cb + ro[i] + co[j], it.u8_min, it.u8_range);
+      for (int j = 0; j < T; ++j) t[i][j] = load_px<U8>(it.src, cb + ro[i] + co[j], u8_min, u8_range);
     float v;
     if constexpr (NS == 0) {
       v = t[0][0];
@@ -255,10 +485,21 @@ bool window_inside(const CganDataTfMap& m, int wh, int ww, int H, int W) {
 extern "C" int cgan_data_transform(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count,
                                    int32_t mode, int32_t src_kind, int32_t epilogue, const float* mean, const float* std,
                                    const float* boundaries, int32_t n_boundaries, void* stream) {
+  return cgan_data_transform_raw(items_host, items_device, count, mode, src_kind, epilogue, mean, std, boundaries,
+                                 n_boundaries, nullptr, stream);
+}
+
+extern "C" int cgan_data_transform_raw(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count,
+                                       int32_t mode, int32_t src_kind, int32_t epilogue, const float* mean, const float* std,
+                                       const float* boundaries, int32_t n_boundaries, const CganDataTfPalette* palette,
+                                       void* stream) {
   CGAN_REQUIRE(items_host && items_device && count > 0 && count <= 65535, "data_transform: bad item table");
   CGAN_REQUIRE(mode == CGAN_DTF_NEAREST || mode == CGAN_DTF_BILINEAR, "data_transform: bad mode %d", mode);
-  CGAN_REQUIRE(src_kind == CGAN_DTF_SRC_B4 || src_kind == CGAN_DTF_SRC_B8 || src_kind == CGAN_DTF_SRC_U8,
-               "data_transform: bad source kind %d", src_kind);
+  CGAN_REQUIRE(src_kind >= CGAN_DTF_SRC_B4 && src_kind <= CGAN_DTF_SRC_SEG_NEAREST, "data_transform: bad source kind %d",
+               src_kind);
+  const bool raw = src_kind >= CGAN_DTF_SRC_UNITY_D;
+  const bool raw_depth = src_kind == CGAN_DTF_SRC_UNITY_D || src_kind == CGAN_DTF_SRC_KITTI_D || src_kind == CGAN_DTF_SRC_F32_D;
+  const bool seg = src_kind == CGAN_DTF_SRC_SEG_EXACT || src_kind == CGAN_DTF_SRC_SEG_NEAREST;
   CGAN_REQUIRE(epilogue == CGAN_DTF_EPI_NONE || epilogue == CGAN_DTF_EPI_NORMALIZE || epilogue == CGAN_DTF_EPI_BUCKETIZE,
                "data_transform: bad epilogue %d", epilogue);
   if (mode == CGAN_DTF_BILINEAR) {
@@ -268,8 +509,19 @@ extern "C" int cgan_data_transform(const CganDataTfItem* items_host, const CganD
   } else {
     CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_U8, "data_transform: uint8 sources are read by the bilinear mode only");
     CGAN_REQUIRE(epilogue != CGAN_DTF_EPI_NORMALIZE, "data_transform: normalize belongs to the bilinear mode");
-    CGAN_REQUIRE(epilogue != CGAN_DTF_EPI_BUCKETIZE || (src_kind == CGAN_DTF_SRC_B4 && boundaries && n_boundaries > 0),
-                 "data_transform: bucketize needs fp32 sources and a boundaries array");
+    CGAN_REQUIRE(epilogue != CGAN_DTF_EPI_BUCKETIZE ||
+                     ((src_kind == CGAN_DTF_SRC_B4 || raw_depth) && boundaries && n_boundaries > 0),
+                 "data_transform: bucketize needs fp32 or raw depth sources and a boundaries array");
+  }
+  CGAN_REQUIRE(!raw || mode == CGAN_DTF_NEAREST, "data_transform: raw sources are read by the nearest mode only");
+  CGAN_REQUIRE(seg == (palette != nullptr), "data_transform: a palette goes with the segmentation kinds, and only with them");
+  CganDataTfPalette pal = {};
+  if (seg) {
+    pal = *palette;
+    CGAN_REQUIRE(pal.n >= 1 && pal.n <= 16, "data_transform: a palette holds 1 to 16 colours, got %d", pal.n);
+    for (int i = 0; i < pal.n; ++i)
+      CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_SEG_EXACT || (pal.colour[i] >> 24) == 0,
+                   "data_transform: palette colour %d of a 3-channel source has an alpha byte", i);
   }
   const int ns = items_host[0].n_stages;
   CGAN_REQUIRE(ns >= 0 && ns <= 2, "data_transform: a plan has 0 to 2 resampling stages, got %d", ns);
@@ -286,7 +538,29 @@ extern "C" int cgan_data_transform(const CganDataTfItem* items_host, const CganD
                              (long)(it.src_w - 1) * it.stride_w < (1l << 31),
                  "data_transform: item %d: source strides outside 32-bit offsets", k);
     CGAN_REQUIRE((long)it.channels * it.out_h * it.out_w < (1l << 31), "data_transform: item %d: output too large", k);
-    CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_U8 || it.u8_range != 0.f, "data_transform: item %d: zero uint8 range", k);
+    CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_U8 || it.stats || it.u8_range != 0.f, "data_transform: item %d: zero uint8 range", k);
+    CGAN_REQUIRE(raw || src_kind == CGAN_DTF_SRC_U8 || !it.stats, "data_transform: item %d: stats go with uint8 and raw sources", k);
+    if (raw) {
+      // the element size is the kind's: the channel count and the strides say what the kernel will read
+      const bool chans = src_kind == CGAN_DTF_SRC_UNITY_D ? (it.channels == 3 || it.channels == 4)
+                         : src_kind == CGAN_DTF_SRC_SEG_EXACT ? it.channels == 3
+                         : src_kind == CGAN_DTF_SRC_SEG_NEAREST ? it.channels == 4
+                         : src_kind == CGAN_DTF_SRC_MASK ? it.channels >= 1 : it.channels == 1;
+      CGAN_REQUIRE(chans, "data_transform: item %d: %d channels do not fit source kind %d", k, it.channels, src_kind);
+      const int known = raw_depth ? (CGAN_DTF_DEC_LOG | CGAN_DTF_DEC_NORMALIZE) : (src_kind == CGAN_DTF_SRC_MASK ? CGAN_DTF_DEC_THRESHOLD : 0);
+      CGAN_REQUIRE((it.dec_flags & ~known) == 0, "data_transform: item %d: decode flags %d do not fit source kind %d", k,
+                   it.dec_flags, src_kind);
+      CGAN_REQUIRE(!((it.dec_flags & CGAN_DTF_DEC_LOG) && (it.dec_flags & CGAN_DTF_DEC_NORMALIZE)),
+                   "data_transform: item %d: normalize and log exclude each other", k);
+      CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_F32_D || !(it.dec_flags & CGAN_DTF_DEC_LOG),
+                   "data_transform: item %d: the fp32 depth is normalised, never log", k);
+      const bool divides = src_kind == CGAN_DTF_SRC_F32_D || (it.dec_flags & CGAN_DTF_DEC_NORMALIZE);
+      CGAN_REQUIRE(!divides || it.stats || it.u8_range != 0.f, "data_transform: item %d: zero range", k);
+      CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_UNITY_D || it.far_plane > 0.f, "data_transform: item %d: far plane %g", k,
+                   (double)it.far_plane);
+      CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_KITTI_D || ((uintptr_t)it.src & 1) == 0, "data_transform: item %d: unaligned uint16 source", k);
+      CGAN_REQUIRE(src_kind != CGAN_DTF_SRC_F32_D || ((uintptr_t)it.src & 3) == 0, "data_transform: item %d: unaligned fp32 source", k);
+    }
     // every window inside the image below it: the sampled indices are clamped to the window, so nothing leaves the source
     int wh = it.out_h, ww = it.out_w;
     for (int s = ns; s >= 0; --s) {
@@ -316,9 +590,24 @@ extern "C" int cgan_data_transform(const CganDataTfItem* items_host, const CganD
   hipLaunchKernelGGL((data_tf_nearest_kernel<E, NS, B>), grid, dim3(256), 0, s, items_device, boundaries, n_boundaries)
 #define NEAR_NS(E, B) \
   do { if (ns == 0) NEAR(E, 0, B); else if (ns == 1) NEAR(E, 1, B); else NEAR(E, 2, B); } while (0)
-    if (epilogue == CGAN_DTF_EPI_BUCKETIZE) NEAR_NS(uint32_t, true);
+#define DEC(K, NS, B) \
+  hipLaunchKernelGGL((data_tf_decode_kernel<K, NS, B>), grid, dim3(256), 0, s, items_device, boundaries, n_boundaries, pal)
+#define DEC_NS(K, B) \
+  do { if (ns == 0) DEC(K, 0, B); else if (ns == 1) DEC(K, 1, B); else DEC(K, 2, B); } while (0)
+#define DEC_B(K) \
+  do { if (epilogue == CGAN_DTF_EPI_BUCKETIZE) DEC_NS(K, true); else DEC_NS(K, false); } while (0)
+    if (src_kind == CGAN_DTF_SRC_UNITY_D) DEC_B(CGAN_DTF_SRC_UNITY_D);
+    else if (src_kind == CGAN_DTF_SRC_KITTI_D) DEC_B(CGAN_DTF_SRC_KITTI_D);
+    else if (src_kind == CGAN_DTF_SRC_F32_D) DEC_B(CGAN_DTF_SRC_F32_D);
+    else if (src_kind == CGAN_DTF_SRC_MASK) DEC_NS(CGAN_DTF_SRC_MASK, false);
+    else if (src_kind == CGAN_DTF_SRC_SEG_EXACT) DEC_NS(CGAN_DTF_SRC_SEG_EXACT, false);
+    else if (src_kind == CGAN_DTF_SRC_SEG_NEAREST) DEC_NS(CGAN_DTF_SRC_SEG_NEAREST, false);
+    else if (epilogue == CGAN_DTF_EPI_BUCKETIZE) NEAR_NS(uint32_t, true);
     else if (src_kind == CGAN_DTF_SRC_B8) NEAR_NS(uint64_t, false);
     else NEAR_NS(uint32_t, false);
+#undef DEC_B
+#undef DEC_NS
+#undef DEC
 #undef NEAR_NS
 #undef NEAR
   } else {
@@ -336,6 +625,43 @@ extern "C" int cgan_data_transform(const CganDataTfItem* items_host, const CganD
 #undef BIL
   }
   CGAN_CHECK_LAUNCH("data_transform");
+  return CGAN_OK;
+}
+
+extern "C" int cgan_data_source_minmax(const CganDataMinmaxItem* items_host, const CganDataMinmaxItem* items_device,
+                                       int32_t count, int32_t src_kind, float* ws, void* stream) {
+  CGAN_REQUIRE(items_host && items_device && ws && count > 0 && count <= 65535, "data_source_minmax: bad item table");
+  CGAN_REQUIRE(src_kind == CGAN_DTF_SRC_U8 || src_kind == CGAN_DTF_SRC_MASK || src_kind == CGAN_DTF_SRC_UNITY_D ||
+                   src_kind == CGAN_DTF_SRC_KITTI_D || src_kind == CGAN_DTF_SRC_F32_D,
+               "data_source_minmax: bad source kind %d", src_kind);
+  const int ch = items_host[0].channels;
+  for (int k = 0; k < count; ++k) {
+    const CganDataMinmaxItem& it = items_host[k];
+    CGAN_REQUIRE(it.src && it.out, "data_source_minmax: item %d: null pointer", k);
+    CGAN_REQUIRE(((uintptr_t)it.src & 15) == 0, "data_source_minmax: item %d: the source is not 16-byte aligned", k);
+    CGAN_REQUIRE(it.pixels > 0 && it.channels > 0 && it.pixels < (1l << 40) / it.channels, "data_source_minmax: item %d: bad size", k);
+    if (src_kind == CGAN_DTF_SRC_UNITY_D) {
+      CGAN_REQUIRE(it.channels == 3 || it.channels == 4, "data_source_minmax: item %d: a Unity depth code has 3 or 4 channels", k);
+      CGAN_REQUIRE(it.channels == ch, "data_source_minmax: item %d has %d channels, item 0 has %d", k, it.channels, ch);
+      CGAN_REQUIRE(it.far_plane > 0.f, "data_source_minmax: item %d: far plane %g", k, (double)it.far_plane);
+    } else if (src_kind == CGAN_DTF_SRC_KITTI_D || src_kind == CGAN_DTF_SRC_F32_D) {
+      CGAN_REQUIRE(it.channels == 1, "data_source_minmax: item %d: a depth map has one channel", k);
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+#define MINMAX(K, CH) \
+  do { \
+    hipLaunchKernelGGL((minmax_partial_kernel<K, CH>), dim3(kParts, count), dim3(256), 0, s, items_device, ws); \
+    CGAN_CHECK_LAUNCH("data_source_minmax_partial"); \
+    hipLaunchKernelGGL((minmax_finish_kernel<K, CH>), dim3(count), dim3(256), 0, s, items_device, (const float*)ws); \
+  } while (0)
+  if (src_kind == CGAN_DTF_SRC_UNITY_D) {
+    if (ch == 3) MINMAX(CGAN_DTF_SRC_UNITY_D, 3); else MINMAX(CGAN_DTF_SRC_UNITY_D, 4);
+  } else if (src_kind == CGAN_DTF_SRC_KITTI_D) MINMAX(CGAN_DTF_SRC_KITTI_D, 1);
+  else if (src_kind == CGAN_DTF_SRC_F32_D) MINMAX(CGAN_DTF_SRC_F32_D, 1);
+  else MINMAX(CGAN_DTF_SRC_U8, 1);
+#undef MINMAX
+  CGAN_CHECK_LAUNCH("data_source_minmax_finish");
   return CGAN_OK;
 }
 

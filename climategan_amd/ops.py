@@ -1601,6 +1601,12 @@ def painter_heads_diffaug_bwd(d_d_in: NHWC, d_vgg_in: Optional[NHWC], m: torch.T
 # ---- training-data transforms (csrc/data_tf.hip) ---------------------------------------------------------------------
 DTF_NEAREST, DTF_BILINEAR = 0, 1
 DTF_EPI_NONE, DTF_EPI_NORMALIZE, DTF_EPI_BUCKETIZE = 0, 1, 2
+DTF_SRC_B4, DTF_SRC_B8, DTF_SRC_U8 = 0, 1, 2
+# raw sources of the nearest mode (include/climategan_hip.h): decoded per gathered pixel
+DTF_SRC_UNITY_D, DTF_SRC_KITTI_D, DTF_SRC_F32_D, DTF_SRC_MASK, DTF_SRC_SEG_EXACT, DTF_SRC_SEG_NEAREST = 3, 4, 5, 6, 7, 8
+DTF_DEC_LOG, DTF_DEC_NORMALIZE, DTF_DEC_THRESHOLD = 1, 2, 4
+_RAW_DTYPES = {DTF_SRC_UNITY_D: "uint8", DTF_SRC_KITTI_D: "uint16", DTF_SRC_F32_D: "float32", DTF_SRC_MASK: "uint8",
+               DTF_SRC_SEG_EXACT: "uint8", DTF_SRC_SEG_NEAREST: "uint8", DTF_SRC_U8: "uint8"}
 JIT_BRIGHTNESS, JIT_SATURATION, JIT_CONTRAST = 1, 2, 3
 
 
@@ -1617,8 +1623,67 @@ def _i32(what, *values):
     return [int(v) for v in values]
 
 
+def raw_dtype(kind):
+    """The torch dtype of a raw source of ``kind``"""
+    return getattr(torch, _RAW_DTYPES[kind])
+
+
+def data_palette(colours, classes, default_class=0):
+    """The by-value table of the segmentation kinds: ``colours`` = up to 16 RGB or RGBA tuples, ``classes`` = the class id of
+    each, ``default_class`` = what a pixel that equals none of them gets (the exact kind only)."""
+    colours, classes = [tuple(int(v) for v in c) for c in colours], [int(c) for c in classes]
+    if not 1 <= len(colours) <= 16 or len(classes) != len(colours):
+        raise RuntimeError("data_palette: 1 to 16 colours and as many classes, got %d and %d" % (len(colours), len(classes)))
+    pal = _lib.DataTfPalette()
+    pal.n, pal.default_class = len(colours), int(default_class)
+    for i, (col, cls) in enumerate(zip(colours, classes)):
+        if len(col) not in (3, 4) or any(not 0 <= v <= 255 for v in col):
+            raise RuntimeError("data_palette: colour %d is %r; 3 or 4 bytes" % (i, col))
+        pal.colour[i] = sum(v << (8 * k) for k, v in enumerate(col))
+        pal.cls[i] = cls
+    return pal
+
+
+def _item_table(items, dev):
+    """The table in device memory.  Pinned + non_blocking, like the optimizer's item table: the host does not wait for the
+    stream.  Neither buffer needs to be kept: the copy and the launch go on the current stream and torch's caching
+    allocators are stream-ordered (a pinned block is not handed out again before the copy that read it has run, a device
+    block not before the work queued on its stream)"""
+    host = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).pin_memory()
+    return host.to(dev, non_blocking=True)
+
+
+def data_source_minmax(sources, kind: int, far=None) -> torch.Tensor:
+    """Whole-source min / max of every sample in two launches and no host synchronisation (cgan_data_source_minmax):
+    returns the [N, 4] fp32 device tensor (min, max - min, max, max > 127) that ``data_transform(..., stats=)`` reads.
+    ``sources``: contiguous raw arrays of ``kind`` ([H, W] or [H, W, C]); ``far``: the Unity far plane per sample."""
+    _need_cuda(*sources)
+    n = len(sources)
+    want = raw_dtype(kind)
+    items = (_lib.DataMinmaxItem * n)()
+    dev = sources[0].device
+    out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    keep = []
+    for k, t in enumerate(sources):
+        if t.dtype != want or t.dim() not in (2, 3) or t.device != dev:
+            raise RuntimeError("data_source_minmax: source kind %d reads %s [H, W] or [H, W, C] arrays, got %s %s"
+                               % (kind, want, tuple(t.shape), t.dtype))
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            t = t.clone(memory_format=torch.contiguous_format)
+            keep.append(t)
+        items[k].src, items[k].out = t.data_ptr(), out[k].data_ptr()
+        items[k].pixels, items[k].channels = t.shape[0] * t.shape[1], (t.shape[2] if t.dim() == 3 else 1)
+        items[k].far_plane = float(far[k]) if far is not None else 0.0
+        if _lib.CALL_LOG is not None:
+            _lib.log_bytes(t.nbytes)
+    ws = torch.empty((n, DIFFAUG_PARTS, 2), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().cgan_data_source_minmax(C.cast(items, C.c_void_p), C.c_void_p(_item_table(items, dev).data_ptr()),
+                                                   n, int(kind), _ptr(ws), _stream()), "cgan_data_source_minmax")
+    return out
+
+
 def data_transform(sources, plans, mode: int, normalize=None, boundaries: Optional[torch.Tensor] = None, u8_ranges=None,
-                   dense=True):
+                   dense=True, raw=None, stats: Optional[torch.Tensor] = None):
     """One launch: sample k's source map through its plan into its own [C, h, w] map (cgan_data_transform).
 
     ``sources``: device tensors, [1, C, H, W] or [C, H, W] with any strides (views are read in place), all fp32, all int32 or
@@ -1626,26 +1691,49 @@ def data_transform(sources, plans, mode: int, normalize=None, boundaries: Option
     sample ``(stages, maps, (out_h, out_w))`` with ``stages`` up to two ``(in_h, in_w, out_h, out_w)`` and ``maps`` =
     len(stages) + 1 triples ``(row_off, col_off, flip)`` (include/climategan_hip.h).  ``normalize`` = (mean, std) per channel
     (bilinear), ``boundaries`` = the fp32 device tensor of torch.bucketize's boundaries (nearest, fp32 in, int32 out).
-    Returns the dense [N, C, h, w] batch, or with ``dense=False`` a list of [1, C, h_k, w_k] maps (sizes may differ)."""
-    _need_cuda(*sources, boundaries)
+    Returns the dense [N, C, h, w] batch, or with ``dense=False`` a list of [1, C, h_k, w_k] maps (sizes may differ).
+
+    Raw sources (nearest mode): ``raw`` = dict(kind=DTF_SRC_*, flags=[DTF_DEC_* bits per sample], far=[far plane per sample]
+    or None, ranges=[(min, range) per sample] or None, palette=``data_palette(...)`` or None) and ``sources`` the arrays as
+    the image decoder left them ([H, W] or [H, W, C] of the kind's dtype); the decode runs on the gathered pixels and the
+    output has one channel (float64 for DTF_SRC_SEG_EXACT, else fp32; int32 with ``boundaries``).  ``stats``: the [N, 4]
+    tensor of ``data_source_minmax`` -- min, range and the mask's threshold flag then come from the device (raw sources, and
+    uint8 ``x`` images, for which ``u8_ranges`` is then None)."""
+    _need_cuda(*sources, boundaries, stats)
     n = len(sources)
     if n == 0 or len(plans) != n:
         raise RuntimeError("data_transform: %d sources, %d plans" % (n, len(plans)))
     dt = sources[0].dtype
     if any(t.dtype != dt or t.device != sources[0].device for t in sources):
         raise RuntimeError("data_transform: the sources of one launch share dtype and device")
-    u8 = u8_ranges is not None
-    if u8:
+    u8 = u8_ranges is not None or (stats is not None and raw is None)
+    if stats is not None and (stats.dtype != torch.float32 or tuple(stats.shape) != (n, 4) or not stats.is_contiguous()):
+        raise RuntimeError("data_transform: stats must be the contiguous [%d, 4] float32 tensor of data_source_minmax" % n)
+    if raw is not None:
+        kind = int(raw["kind"])
+        if kind not in _RAW_DTYPES or kind == DTF_SRC_U8:
+            raise RuntimeError("data_transform: %d is no raw source kind" % kind)
+        if u8_ranges is not None or normalize is not None or mode != DTF_NEAREST:
+            raise RuntimeError("data_transform: raw sources are read by the nearest mode, without u8_ranges or normalize")
+        if dt != raw_dtype(kind) or any(t.dim() not in (2, 3) for t in sources):
+            raise RuntimeError("data_transform: source kind %d reads %s [H, W] or [H, W, C] arrays, got %s"
+                               % (kind, raw_dtype(kind), dt))
+        if len(raw["flags"]) != n:
+            raise RuntimeError("data_transform: %d sources, %d decode flags" % (n, len(raw["flags"])))
+        if boundaries is not None and kind not in (DTF_SRC_UNITY_D, DTF_SRC_KITTI_D, DTF_SRC_F32_D):
+            raise RuntimeError("data_transform: bucketize reads depth sources")
+    elif u8:
         if dt != torch.uint8 or mode != DTF_BILINEAR or any(t.dim() != 3 for t in sources):
             raise RuntimeError("data_transform: u8_ranges go with uint8 [H, W, C] sources in the bilinear mode")
         kind = 2
     elif dt in (torch.float32, torch.int32):
         kind = 0
-    elif dt == torch.int64:
+    elif dt in (torch.int64, torch.float64):   # float64: the kitti segmentation map of process_kitti_seg
         kind = 1
     else:
-        raise RuntimeError("data_transform: sources must be float32, int32, int64 or (with u8_ranges) uint8, got %s" % dt)
-    if (mode == DTF_BILINEAR or boundaries is not None) and not u8 and dt != torch.float32:
+        raise RuntimeError("data_transform: sources must be float32, int32, int64, float64 or (with u8_ranges) uint8, got %s"
+                           % dt)
+    if (mode == DTF_BILINEAR or boundaries is not None) and not u8 and raw is None and dt != torch.float32:
         raise RuntimeError("data_transform: the bilinear mode and bucketize read float32 maps, got %s" % dt)
     epi = DTF_EPI_NONE
     mean = std = None
@@ -1656,10 +1744,15 @@ def data_transform(sources, plans, mode: int, normalize=None, boundaries: Option
             raise RuntimeError("data_transform: boundaries must be a contiguous 1-D float32 tensor")
         epi = DTF_EPI_BUCKETIZE
     out_dt = torch.int32 if boundaries is not None else (torch.float32 if mode == DTF_BILINEAR else dt)
+    if raw is not None and boundaries is None:
+        out_dt = torch.float64 if kind == DTF_SRC_SEG_EXACT else torch.float32
     items = (_lib.DataTfItem * n)()
     shapes, total = [], 0
     for k, (t, (stages, maps, (oh, ow))) in enumerate(zip(sources, plans)):
-        if u8:
+        if raw is not None:
+            (h, w), (sh, sw) = t.shape[:2], t.stride()[:2]
+            c, sc = (t.shape[2], t.stride(2)) if t.dim() == 3 else (1, 0)
+        elif u8:
             (h, w, c), (sh, sw, sc) = t.shape, t.stride()
         else:
             if t.dim() == 4:
@@ -1677,8 +1770,16 @@ def data_transform(sources, plans, mode: int, normalize=None, boundaries: Option
         it.stride_c, it.stride_h, it.stride_w = _i32("source stride", sc, sh, sw)
         it.out_h, it.out_w = _i32("output size", oh, ow)
         it.n_stages = len(stages)
-        if u8:
+        if u8_ranges is not None:
             it.u8_min, it.u8_range = float(u8_ranges[k][0]), float(u8_ranges[k][1])
+        if raw is not None:
+            it.dec_flags = int(raw["flags"][k])
+            it.far_plane = float(raw["far"][k]) if raw.get("far") is not None else 0.0
+            if raw.get("ranges") is not None and raw["ranges"][k] is not None:
+                it.u8_min, it.u8_range = float(raw["ranges"][k][0]), float(raw["ranges"][k][1])
+            c = 1                                   # the decoded map has one channel
+        if stats is not None:
+            it.stats = stats[k].data_ptr()
         for i, st in enumerate(stages):
             it.stage[i] = _lib.DataTfStage(*_i32("stage size", *st))
         for i, m in enumerate(maps):
@@ -1697,17 +1798,13 @@ def data_transform(sources, plans, mode: int, normalize=None, boundaries: Option
     for k, (c, oh, ow) in enumerate(shapes):
         items[k].dst = flat.data_ptr() + off * flat.element_size()
         off += c * oh * ow
-    # pinned + non_blocking, like the optimizer's item table: the host does not wait for the stream.  Neither buffer needs
-    # to be kept: the copy and the launch go on the current stream and torch's caching allocators are stream-ordered (a
-    # pinned block is not handed out again before the copy that read it has run, a device block not before the work queued
-    # on its stream)
-    host = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).pin_memory()
-    table = host.to(dev, non_blocking=True)
-    _lib.check(_lib.load().cgan_data_transform(C.cast(items, C.c_void_p), C.c_void_p(table.data_ptr()), n, int(mode), kind, epi,
-                                               C.cast(mean, C.c_void_p) if mean is not None else None,
-                                               C.cast(std, C.c_void_p) if std is not None else None,
-                                               _ptr(boundaries), 0 if boundaries is None else boundaries.numel(), _stream()),
-               "cgan_data_transform")
+    table = _item_table(items, dev)
+    palette = raw.get("palette") if raw is not None else None
+    _lib.check(_lib.load().cgan_data_transform_raw(
+        C.cast(items, C.c_void_p), C.c_void_p(table.data_ptr()), n, int(mode), kind, epi,
+        C.cast(mean, C.c_void_p) if mean is not None else None, C.cast(std, C.c_void_p) if std is not None else None,
+        _ptr(boundaries), 0 if boundaries is None else boundaries.numel(),
+        C.cast(C.pointer(palette), C.c_void_p) if palette is not None else None, _stream()), "cgan_data_transform")
     if dense:
         return flat.view(n, *shapes[0])
     outs, off = [], 0

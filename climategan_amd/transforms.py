@@ -10,7 +10,10 @@ random draws in the reference's order, reduces each task's flips, crops and resi
 up to two resampling stages with an integer index map before, between and after them) and runs ONE launch per task for the
 whole batch (``ops.data_transform``, csrc/data_tf.hip), which reads only the source pixels the final crop needs and
 writes the collated ``[N, C, h, w]`` batch ``Trainer.train_step`` takes.  The index arithmetic is ATen's own fp32
-formulas, so ``d``, ``m``, ``s`` equal the reference bit for bit and ``x`` to a few fp32 roundings.
+formulas, so ``d``, ``m``, ``s`` equal the reference bit for bit and ``x`` to a few fp32 roundings.  A sample's entries may
+also be ``RawSource``s -- the arrays as the image decoder left them (Unity / kitti / fp32 depth, uint8 mask, RGB or RGBA
+segmentation image, uint8 ``x``): the same launch then decodes the pixels it gathers (``tensor_loader``'s work,
+``climategan_amd.data``), and only a min / max that nobody knows costs two launches more.
 
 The colour jitter of the pipeline (the ``is_diff_augment=False`` branches of ``rand_brightness / rand_saturation /
 rand_contrast``, ``transforms.py:501-541``) calls torchvision's ``adjust_*``.  No run of the reference backs this part:
@@ -334,6 +337,107 @@ class U8Image:
         return _run_one(self.t, Plan(h, w), ops.DTF_BILINEAR, u8_ranges=[(self.min, self.range)])
 
 
+class RawSource:
+    """A ``d``, ``m``, ``s`` or ``x`` source as the image decoder left it: the raw device array and what it encodes.  The
+    gather decodes the pixels it reads (``ops.data_transform(raw=...)``, csrc/data_tf.hip), so nothing passes over the whole
+    source on the host; the one thing that has to see every pixel -- the min / max of a normalised depth, of ``x``, and the
+    mask's "max > 127" -- is two launches on the raw bytes (``ops.data_source_minmax``) unless the caller knows it.
+
+    ``kind``:
+      "unity_d"    uint8 [H, W, 3 or 4]: Unity's depth code (tutils.py:237-293), with ``far``, ``log``, ``normalize``
+      "kitti_d"    uint16 [H, W]: centimetres (tutils.py:207-217), with ``log``, ``normalize``
+      "f32_d"      float32 [H, W]: the real domain's depth, min-max normalised (tutils.py:197-201)
+      "mask"       uint8 [H, W] or [H, W, C]: ``> 127`` when the file's max is above 127, channel 0 (data.py:391-397);
+                   ``threshold`` = that flag when the caller knows it
+      "kitti_s"    uint8 [H, W, 3]: ``process_kitti_seg`` (data.py:129-148), float64 class ids
+      "palette_s"  uint8 [H, W, 4] RGBA: ``encode_segmap`` (data.py:231-252) for ``domain`` "s" or "r", fp32 class ids
+      "x"          uint8 [H, W, 3 or 4]: ``arr -= arr.min(); arr /= arr.max()`` (data.py:385-387); a ``U8Image`` whose min
+                   and max are found on the device
+    ``minmax`` = the known (min, max) of the decoded map (of the raw bytes for "x").  A fourth channel of "x" and "mask" is
+    dropped first, as tensor_loader does (data.py:382-383)."""
+
+    KINDS = {"unity_d": ops.DTF_SRC_UNITY_D, "kitti_d": ops.DTF_SRC_KITTI_D, "f32_d": ops.DTF_SRC_F32_D,
+             "mask": ops.DTF_SRC_MASK, "kitti_s": ops.DTF_SRC_SEG_EXACT, "palette_s": ops.DTF_SRC_SEG_NEAREST,
+             "x": ops.DTF_SRC_U8}
+    TASKS = {"unity_d": "d", "kitti_d": "d", "f32_d": "d", "mask": "m", "kitti_s": "s", "palette_s": "s", "x": "x"}
+
+    def __init__(self, arr, kind, far=1000, log=False, normalize=False, minmax=None, threshold=None, palette=None):
+        if kind not in self.KINDS:
+            raise ValueError("RawSource: kind %r; one of %s" % (kind, sorted(self.KINDS)))
+        assert not (normalize and log)                                          # tutils.py:196
+        code = self.KINDS[kind]
+        dims = {"unity_d": (3,), "kitti_d": (2,), "f32_d": (2,), "mask": (2, 3), "kitti_s": (3,), "palette_s": (3,), "x": (3,)}
+        if arr.dtype != ops.raw_dtype(code) or arr.dim() not in dims[kind]:
+            raise RuntimeError("RawSource: %r is a %s array of %s dimensions, got %s %s"
+                               % (kind, ops.raw_dtype(code), " or ".join(map(str, dims[kind])), tuple(arr.shape), arr.dtype))
+        chans = {"unity_d": (3, 4), "kitti_s": (3,), "palette_s": (4,), "x": (3, 4)}
+        if kind in chans and arr.shape[2] not in chans[kind]:
+            raise RuntimeError("RawSource: %r has %s channels, got %d" % (kind, " or ".join(map(str, chans[kind])), arr.shape[2]))
+        if kind in ("x", "mask") and arr.dim() == 3 and arr.shape[2] == 4:
+            arr = arr[:, :, :3]
+        if kind in ("kitti_s", "palette_s") and palette is None:
+            raise ValueError("RawSource: %r needs its palette (climategan_amd.data builds it)" % kind)
+        self.t, self.kind, self.code, self.palette = arr, kind, code, palette
+        self.far, self.log = float(far), bool(log)
+        self.normalize = bool(normalize) or kind == "f32_d"
+        self.threshold = None if threshold is None else bool(threshold)
+        self.min = self.range = None
+        if minmax is not None:
+            # ``t - min`` then ``/ max(t - min)``: the divisor is the fp32 difference
+            self.min = float(np.float32(minmax[0]))
+            self.range = float(np.float32(minmax[1]) - np.float32(minmax[0]))
+
+    @classmethod
+    def from_numpy(cls, arr, kind, device, **kw):
+        return cls(torch.from_numpy(np.ascontiguousarray(arr)).to(device), kind, **kw)
+
+    @property
+    def task(self):
+        return self.TASKS[self.kind]
+
+    @property
+    def shape(self):
+        return (1, 3 if self.kind == "x" else 1, int(self.t.shape[0]), int(self.t.shape[1]))
+
+    @property
+    def needs_stats(self):
+        """Whether the launch needs this sample's whole-source min / max from the device"""
+        if self.kind == "mask":
+            return self.threshold is None
+        if self.kind == "x" or (self.normalize and self.kind in ("unity_d", "kitti_d", "f32_d")):
+            return self.min is None
+        return False
+
+    @property
+    def flags(self):
+        return ((ops.DTF_DEC_LOG if self.log else 0) | (ops.DTF_DEC_NORMALIZE if self.normalize and self.kind != "f32_d" else 0)
+                | (ops.DTF_DEC_THRESHOLD if self.threshold else 0))
+
+    def to_tensor(self):
+        """``tensor_loader``'s [1, C, H, W] tensor: the identity plan through the same kernel"""
+        _, _, h, w = self.shape
+        return _run_raw([self], [Plan(h, w).launches()[0]])
+
+
+def _run_raw(sources, plans, dense=True, **kw):
+    """One launch over raw sources of one kind (plus the two min / max launches when a sample needs them)"""
+    first = sources[0]
+    table = None if first.palette is None else bytes(first.palette)
+    if any(s.kind != first.kind or (None if s.palette is None else bytes(s.palette)) != table for s in sources):
+        raise TypeError("BatchTransform: one launch reads one kind of source with one palette, got %s"
+                        % sorted({s.kind for s in sources}))
+    arrays = [s.t for s in sources]
+    stats = None
+    if any(s.needs_stats for s in sources):
+        stats = ops.data_source_minmax(arrays, first.code, far=[s.far for s in sources])
+    if first.kind == "x":
+        ranges = None if stats is not None else [(s.min, s.range) for s in sources]
+        return ops.data_transform(arrays, plans, ops.DTF_BILINEAR, u8_ranges=ranges, stats=stats, dense=dense, **kw)
+    raw = dict(kind=first.code, flags=[s.flags for s in sources], far=[s.far for s in sources], palette=first.palette,
+               ranges=[(s.min, s.range) if s.min is not None else None for s in sources])
+    return ops.data_transform(arrays, plans, ops.DTF_NEAREST, raw=raw, stats=stats, dense=dense, **kw)
+
+
 def _hw(v):
     return tuple(int(a) for a in v.shape[-2:])
 
@@ -358,6 +462,9 @@ def _tensors_only(data, who):
         if isinstance(v, U8Image):
             raise TypeError("%s: %r is a U8Image; the per-sample transforms take tensors -- call .to_float() first, or use "
                             "compile_transforms, which reads the uint8 image directly" % (who, task))
+        if isinstance(v, RawSource):
+            raise TypeError("%s: %r is a RawSource; the per-sample transforms take tensors -- call .to_tensor() first, or use "
+                            "compile_transforms, which reads the raw array directly" % (who, task))
 
 
 def _run_one(tensor, plan, mode, **kw):
@@ -613,7 +720,7 @@ class Compose:
 
 class BatchTransform:
     """The transform list of ``get_transforms`` on a whole batch: ``batch(samples)`` with ``samples`` a list of N dicts
-    ``{task: [1, C, H, W] device tensor}`` (``x`` may be a ``U8Image``) returns ``{task: [N, C, h, w]}``, the reference's
+    ``{task: [1, C, H, W] device tensor}`` (``x`` may be a ``U8Image``, any task a ``RawSource`` of its kind) returns ``{task: [N, C, h, w]}``, the reference's
     collated batch.  Per sample it makes the reference's draws in the reference's order and reduces every task's flips,
     crops and resizes to a ``Plan`` on the host; then each task is ONE launch for the whole batch (one more per two further
     resizes beyond the second), plus one launch per colour-jitter item on ``x`` (two for contrast: its mean)."""
@@ -672,6 +779,10 @@ class BatchTransform:
             if n_u8 not in (0, len(sources)) or (n_u8 and task != "x"):
                 raise TypeError("BatchTransform: %r is a U8Image in %d of %d samples; one launch reads one kind of source "
                                 "(all uint8 images, x only, or all tensors)" % (task, n_u8, len(sources)))
+            n_raw = sum(isinstance(v, RawSource) for v in sources)
+            if n_raw not in (0, len(sources)) or any(isinstance(v, RawSource) and v.task != task for v in sources):
+                raise TypeError("BatchTransform: %r is a RawSource in %d of %d samples, or of another task's kind; one "
+                                "launch reads one kind of source" % (task, n_raw, len(sources)))
             if n_u8:
                 u8 = [(s.min, s.range) for s in sources]
                 sources = [s.t for s in sources]
@@ -683,8 +794,11 @@ class BatchTransform:
                 if last and task == "x" and norm is not None and not jitter:
                     kw["normalize"] = (norm.mean, norm.std)
                 if last and task == "d" and bucket is not None:
-                    kw["boundaries"] = bucket.boundaries(sources[0].device)
-                sources = ops.data_transform(sources, [c[i] for c in chunks], mode, u8_ranges=u8, dense=last, **kw)
+                    kw["boundaries"] = bucket.boundaries((sources[0].t if n_raw and i == 0 else sources[0]).device)
+                if n_raw and i == 0:        # the decode belongs to the launch that reads the source
+                    sources = _run_raw(sources, [c[i] for c in chunks], dense=last, **kw)
+                else:
+                    sources = ops.data_transform(sources, [c[i] for c in chunks], mode, u8_ranges=u8, dense=last, **kw)
                 u8 = None
             y = sources
             if task == "x":

@@ -6,6 +6,7 @@ hot path itself the last two never run as torch expressions: ``make_m_cond`` (``
 conversion (``cgan_normalize_u8_nhwc``) and the Painter heads (``cgan_painter_heads_fwd``: paste + D input +
 VGG pre-processing in one kernel) have them fused.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.nn import init
@@ -125,3 +126,35 @@ def divide_pred(disc_output):
         half2 = [[_half(t, False) for t in p] for p in disc_output]
         return half1, half2
     return _half(disc_output, True), _half(disc_output, False)
+
+
+def _raw_depth(tensor, dtype):
+    """The raw integer array of a depth source: the reference's callers hand over ``arr.astype(np.float32)`` (data.py:364);
+    such a float tensor holds the file's integers and goes back to them (a cast, no decode)"""
+    return tensor if tensor.dtype == dtype else tensor.to(dtype)
+
+
+def get_normalized_depth_t(tensor, domain, normalize=False, log=True):
+    """reference tutils.py:195-219 on the device: the raw depth array of ``domain`` ("r": float32 H x W, "s": H x W x 3 Unity
+    code, "kitti": H x W centimetres; the integer arrays as uint8 / uint16 or as the float tensor the reference's loader
+    makes of them) -> the 1 x H x W float32 depth.  One identity-plan launch of the data gather (two more for a min / max)."""
+    from .transforms import RawSource
+    assert not (normalize and log)
+    if domain == "r":
+        return RawSource(tensor.float(), "f32_d").to_tensor()[0]
+    if domain == "s":
+        return decode_unity_depth_t(tensor, log=log, normalize=normalize)
+    if domain == "kitti":
+        return RawSource(_raw_depth(tensor, torch.uint16), "kitti_d", log=log, normalize=normalize).to_tensor()[0]
+    return tensor
+
+
+def decode_unity_depth_t(unity_depth, log=True, normalize=False, numpy=False, far=1000):
+    """reference tutils.py:237-293: the 3-channel depth code of the Unity simulator -> 1 x H x W metric depth (``1 / depth``,
+    or ``log(depth)``; min-max normalised on request).  ``numpy=True`` is the reference's display branch and stays on the
+    host: the decoded map as a uint8 array."""
+    from .transforms import RawSource
+    depth = RawSource(_raw_depth(unity_depth, torch.uint8), "unity_d", far=far, log=log, normalize=normalize).to_tensor()[0]
+    if numpy:
+        return depth.data.cpu().numpy().astype(np.uint8).squeeze()
+    return depth

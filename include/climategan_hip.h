@@ -831,6 +831,16 @@ int cgan_pair_copy_channels(const void* src3, void* dst3, int32_t dtype, int64_t
 #define CGAN_DTF_SRC_B4 0  /* 4-byte elements: fp32 (the only one bilinear and bucketize take), int32 */
 #define CGAN_DTF_SRC_B8 1  /* 8-byte elements: int64 */
 #define CGAN_DTF_SRC_U8 2  /* uint8, bilinear only */
+/* raw sources of the nearest mode, decoded per gathered pixel (see "raw sources" below) */
+#define CGAN_DTF_SRC_UNITY_D 3     /* uint8 HWC, 3 or 4 channels: Unity's depth code -> fp32 */
+#define CGAN_DTF_SRC_KITTI_D 4     /* uint16 HW: centimetres -> fp32 */
+#define CGAN_DTF_SRC_F32_D 5       /* fp32 HW: (v - min) / range */
+#define CGAN_DTF_SRC_MASK 6        /* uint8 HW or HWC (channel 0) -> fp32 */
+#define CGAN_DTF_SRC_SEG_EXACT 7   /* uint8 HWC, 3 channels: exact palette hit -> class id, float64 */
+#define CGAN_DTF_SRC_SEG_NEAREST 8 /* uint8 HWC, 4 channels: nearest palette colour -> class id, fp32 */
+#define CGAN_DTF_DEC_LOG 1       /* depth kinds: log(depth) instead of 1 / depth */
+#define CGAN_DTF_DEC_NORMALIZE 2 /* Unity / kitti depth: (v - min) / range after 1 / depth (never with LOG) */
+#define CGAN_DTF_DEC_THRESHOLD 4 /* mask: v > 127 ? 1 : 0 (the host knows that the file's max exceeds 127) */
 #define CGAN_DTF_EPI_NONE 0
 #define CGAN_DTF_EPI_NORMALIZE 1
 #define CGAN_DTF_EPI_BUCKETIZE 2
@@ -853,7 +863,51 @@ typedef struct {
   float u8_min, u8_range;
   CganDataTfStage stage[2];
   CganDataTfMap map[3];
+  /* raw sources (zero for everything above).  stats: NULL, or the sample's 4 floats written by cgan_data_source_minmax
+   * on the same stream; then (min, range) and the mask's threshold flag come from there and u8_min / u8_range /
+   * CGAN_DTF_DEC_THRESHOLD are not read. */
+  const float* stats;
+  float far_plane; /* Unity depth: the camera's far plane */
+  int32_t dec_flags;
 } CganDataTfItem;
+/* Raw sources: what tensor_loader decodes on the host (data.py:91-148, 231-252, 344-399; tutils.py:195-293), applied to the
+ * gathered pixel only.  All fp32 operations are IEEE-exact (no contraction, no reciprocal approximation); log is evaluated in
+ * float64 on the fp32 depth and rounded to fp32.
+ *   UNITY_D      R = (247 - R) / 8 and G likewise (int division truncating toward zero: 248..254 -> 0, 255 -> -1), B = 255 - B,
+ *                code = R * 256 * 31 + G * 256 + B, depth = (float)code / 246015.f * far_plane; then 1 / depth, or log(depth)
+ *   KITTI_D      depth = (float)v / 100.f; then 1 / depth, or log(depth)
+ *   F32_D        (v - min) / range
+ *   with CGAN_DTF_DEC_NORMALIZE the inverse depth becomes (v - min) / range; CGAN_DTF_EPI_BUCKETIZE applies to all three
+ *   MASK         threshold ? (v > 127 ? 1 : 0) : (float)v, channel 0
+ *   SEG_EXACT    the class of the palette colour that equals the pixel, else default_class (process_kitti_seg: the kitti
+ *                label lookup and the label merge folded into one table)
+ *   SEG_NEAREST  the class of the palette colour at the smallest squared distance in exact integers; the first one wins a tie
+ * palette: by value, colour[i] = R | G << 8 | B << 16 | A << 24 (A = 0 for 3-channel sources). */
+typedef struct {
+  int32_t n; /* 1..16 */
+  int32_t default_class;
+  uint32_t colour[16];
+  int32_t cls[16];
+} CganDataTfPalette;
+/* cgan_data_transform with the raw source kinds: the same call plus the palette (NULL unless a SEG kind). */
+int cgan_data_transform_raw(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count, int32_t mode,
+                            int32_t src_kind, int32_t epilogue, const float* mean, const float* std, const float* boundaries,
+                            int32_t n_boundaries, const CganDataTfPalette* palette, void* stream);
+/* Whole-source min / max of `count` samples in two launches (fixed-range partials, then a fixed-order finish; no atomics, no
+ * host synchronisation): out[0] = min, out[1] = max - min in fp32, out[2] = max, out[3] = max > 127 ? 1 : 0, of
+ *   CGAN_DTF_SRC_U8 / MASK  every byte of the array as a float (tensor_loader's arr.min() / arr.max(), all channels)
+ *   UNITY_D / KITTI_D       the inverse depth 1 / depth of every pixel, in the gather's own arithmetic
+ *   F32_D                   every value
+ * NaN propagates like torch.min / torch.max.  src: contiguous and 16-byte aligned; ws: count * 2 * CGAN_DIFFAUG_PARTS floats. */
+typedef struct {
+  const void* src;
+  float* out;      /* device, 4 floats */
+  int64_t pixels;  /* src_h * src_w */
+  int32_t channels;
+  float far_plane;
+} CganDataMinmaxItem;
+int cgan_data_source_minmax(const CganDataMinmaxItem* items_host, const CganDataMinmaxItem* items_device, int32_t count,
+                            int32_t src_kind, float* ws, void* stream);
 int cgan_data_transform(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count, int32_t mode,
                         int32_t src_kind, int32_t epilogue, const float* mean, const float* std, const float* boundaries,
                         int32_t n_boundaries, void* stream);
