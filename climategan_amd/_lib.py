@@ -57,6 +57,11 @@ class AdamItem(C.Structure):
                 ("numel", C.c_int64)]
 
 
+class AmpOptimItem(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("step", C.c_void_p),
+                ("numel", C.c_int64)]
+
+
 class DataTfMap(C.Structure):
     _fields_ = [("row_off", C.c_int32), ("col_off", C.c_int32), ("flip", C.c_int32)]
 
@@ -156,6 +161,10 @@ _SIGNATURES = {
     "cgan_spectral_norm_power_iter_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "cgan_extra_adam_multi_tensor": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                                C.c_double, C.c_double, C.c_double, C.c_double, _P]),
+    "cgan_grads_nonfinite_check_multi_tensor": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_double, C.c_int32, _P, _P]),
+    "cgan_adam_multi_tensor": (C.c_int, [_P, C.c_int32, C.c_int64] + [C.c_double] * 6 + [_P, _P]),
+    "cgan_rmsprop_multi_tensor": (C.c_int, [_P, C.c_int32, C.c_int64] + [C.c_double] * 5 + [_P, _P]),
+    "cgan_amp_optim_finish": (C.c_int, [_P, C.c_int32, _P, _P]),
     "cgan_nchw_to_nhwc": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "cgan_nhwc_to_nchw": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "cgan_resize_nearest_nhwc": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -84,6 +84,7 @@ def default_opts() -> Opts:
         # shared/trainer/events.yaml:1-14
         "val": {"val_painter": "none"},   # :323 (a cluster path in the reference: "none" here = no validation painter)
         "train": {"save_n_epochs": 25, "min_save_epoch": 28, "resume": False,   # :313-315
+                  "amp": False,                                                   # :268
                   "lambdas": {"advent": {"ent_main": 0.5, "ent_aux": 0.0, "ent_var": 0.1, "adv_main": 1.0,
                                          "adv_aux": 0.0, "dis_main": 1.0, "dis_aux": 0.0},      # :303-310
                               "G": {"d": {"main": 1, "gml": 0.5},

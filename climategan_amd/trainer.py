@@ -85,6 +85,17 @@ class Trainer:
         self._side = None
         # development aid (tools/branch_times.py): [(fork event, end of the main-stream branch, end of the side-stream branch)]
         self.branch_events = [] if os.environ.get("CGAN_BRANCH_TIMES") == "1" else None
+        # train.amp (reference trainer.py:116-126): fp16 compute with one dynamic loss scaler per model.  The scalers are
+        # not checkpointed (the reference's save() does not either, trainer.py:403-420): a resumed run starts again at the
+        # initial scale.
+        self.grad_scaler_g = self.grad_scaler_d = None
+        if opts.train.get("amp", False):
+            optimizers = [str(opts.gen.opt.optimizer).lower(), str(opts.dis.opt.optimizer).lower()]
+            if "extraadam" in optimizers:
+                raise ValueError("AMP does not work with ExtraAdam ({})".format(optimizers))
+            from .optim import GradScaler
+            self.grad_scaler_d = GradScaler()
+            self.grad_scaler_g = GradScaler()
 
     def setup(self, inference=False):
         """reference trainer.py:701-789."""
@@ -108,9 +119,11 @@ class Trainer:
         self.D = create_discriminator(o, self.device, verbose=self.verbose)
         self.G.train()
         self.D.train()
-        # 16-bit activation GRADIENTS: the masker's loss weights (1e-3 / (n h w)) underflow fp16; bf16 has the range
-        self.G.set_compute_dtype(torch.bfloat16)
-        self.D.set_compute_dtype(torch.bfloat16)
+        # 16-bit activation GRADIENTS: the masker's loss weights (1e-3 / (n h w)) underflow fp16; bf16 has the range.
+        # train.amp is the reference's fp16 mode: the range comes from the dynamic loss scale (grad_scaler_g / _d)
+        dtype = torch.float16 if self.grad_scaler_g is not None else torch.bfloat16
+        self.G.set_compute_dtype(dtype)
+        self.D.set_compute_dtype(dtype)
         self.domain_labels = {"s": 0, "r": 1}                          # trainer.py:107
         self.has_masker = any(t in o.tasks for t in "msd")
         # get_losses (losses.py:353-441).  Note: losses["D"]["p"] IS losses["G"]["p"]["gan"] (one GANLoss object), so
@@ -605,7 +618,12 @@ class Trainer:
         self._check_batch(multi_domain_batch)
         for p in self.D.parameters():                                   # trainer.py:959-962
             p.requires_grad_(False)
+        scaler = self.grad_scaler_g
         try:
+            if scaler is not None:
+                # train.amp (trainer.py:1004-1009): the loss kernels fold the scale into their gradients; both branches
+                # of this update share it
+                ag.set_grad_scale(scaler.get_scale())
             self.g_opt.zero_grad(set_to_none=True)
             g_loss = 0                                                  # get_G_loss, trainer.py:1162-1182
             do_m = self.has_masker and any(d != "rf" for d in multi_domain_batch)
@@ -640,12 +658,15 @@ class Trainer:
                 self._backward(g_loss, self.G)
             if self.g_reducer is not None:
                 self.g_reducer.finish()                                 # before extrapolation AND step (trainer.py:678-683)
-            self._unscale_grads(self.G)
-            if self.global_step % 2 == 0:
-                self.g_opt.extrapolation()
+            if scaler is not None:
+                scaler.step(self.g_opt)       # check -> update (unscales in registers) -> finish; no host wait
+                scaler.update()
             else:
-                self.g_opt.step()
+                self._unscale_grads(self.G)
+                self.g_opt_step()
         finally:
+            if scaler is not None:
+                ag.set_grad_scale(1.0)
             self._restore_d_grad_flags()                                # trainer.py:971-973
         return g_loss.detach()
 
@@ -715,6 +736,21 @@ class Trainer:
             if grads:
                 torch._foreach_mul_(grads, 1.0 / ag.GRAD_SCALE)
 
+    def g_opt_step(self):
+        """reference trainer.py:674-683: with an extragradient optimizer, extrapolate on even steps and step on odd ones;
+        any other optimizer steps on every iteration."""
+        if "extra" in str(self.opts.gen.opt.optimizer).lower() and self.global_step % 2 == 0:
+            self.g_opt.extrapolation()
+        else:
+            self.g_opt.step()
+
+    def d_opt_step(self):
+        """reference trainer.py:685-694."""
+        if "extra" in str(self.opts.dis.opt.optimizer).lower() and self.global_step % 2 == 0:
+            self.d_opt.extrapolation()
+        else:
+            self.d_opt.step()
+
     def _restore_d_grad_flags(self):
         for name, p in self.D.named_parameters():
             p.requires_grad_(not (name.endswith("weight_u") or name.endswith("weight_v")))
@@ -722,6 +758,16 @@ class Trainer:
     def update_D(self, multi_domain_batch):
         """reference trainer.py:1017-1032 + d_opt_step (685-694)."""
         self._check_batch(multi_domain_batch)
+        scaler = self.grad_scaler_d
+        if scaler is None:
+            return self._update_D(multi_domain_batch, None)
+        ag.set_grad_scale(scaler.get_scale())                           # train.amp, trainer.py:1020-1025
+        try:
+            return self._update_D(multi_domain_batch, scaler)
+        finally:
+            ag.set_grad_scale(1.0)
+
+    def _update_D(self, multi_domain_batch, scaler):
         self.d_opt.zero_grad(set_to_none=True)
         d_loss = 0
         do_p = self.has_painter and "rf" in multi_domain_batch
@@ -748,11 +794,12 @@ class Trainer:
             self._backward(d_loss, self.D)
         if self.d_reducer is not None:
             self.d_reducer.finish()
-        self._unscale_grads(self.D)
-        if self.global_step % 2 == 0:
-            self.d_opt.extrapolation()
+        if scaler is not None:
+            scaler.step(self.d_opt)
+            scaler.update()
         else:
-            self.d_opt.step()
+            self._unscale_grads(self.D)
+            self.d_opt_step()
         return d_loss.detach()
 
     def train_step(self, multi_domain_batch):
@@ -953,7 +1000,9 @@ class Trainer:
     def save(self):
         """reference trainer.py:396-420: ``{epoch, G, g_opt, step[, D, d_opt]}`` to ``<output_path>/checkpoints/
         latest_ckpt.pth`` every call, plus ``epoch_<n>_ckpt.pth`` when ``epoch >= min_save_epoch`` and ``epoch %
-        save_n_epochs == 0``.  Same keys, same state-dict layouts: the reference's ``resume`` reads these files."""
+        save_n_epochs == 0``.  Same keys, same state-dict layouts: the reference's ``resume`` reads these files.  Adam /
+        RMSprop state travels through ``g_opt`` / ``d_opt`` like ExtraAdam's (``step`` as a tensor).  The loss scalers of
+        ``train.amp`` are NOT saved, as in the reference: a resumed run starts again at their initial scale."""
         from pathlib import Path
 
         save_dir = Path(self.opts.output_path) / "checkpoints"
@@ -1016,7 +1065,8 @@ class Trainer:
     def resume(self, inference=False):
         """reference trainer.py:422-579: load G (``strict=False`` with warnings in inference mode, then stop), g_opt,
         replay the schedulers ``epoch + 1`` times, D and d_opt, epoch / step, and round the step up to an even number
-        (extragradient: extrapolation happens on even steps)."""
+        (extragradient: extrapolation happens on even steps).  ``grad_scaler_g`` / ``grad_scaler_d`` (``train.amp``) are not
+        part of a checkpoint: they keep the state they have, the initial scale in a fresh process."""
         checkpoint = self._resolve_checkpoint()
         if inference:
             bad = self.G.load_state_dict(checkpoint["G"], strict=False)

@@ -280,6 +280,41 @@ int cgan_extra_adam_multi_tensor(const CganAdamItem* items_device, int32_t count
                                  double weight_decay, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Adam / RMSprop (torch.optim; the reference's get_optimizer, climategan/optim.py:110-121) and the dynamic loss scaling
+ * of train.amp (torch's GradScaler; trainer.py:116-126, 1004-1009, 1020-1025), fused over all parameter tensors.
+ * One optimizer step = check -> update -> finish, three launches on `stream` that the host never waits for:
+ *   cgan_grads_nonfinite_check_multi_tensor  *found_inf_device = 1.0f if any gradient element is +-inf or NaN (it is never
+ *       cleared here); write_back = 1 also stores g * inv_scale (GradScaler.unscale_), 0 writes nothing else.
+ *   cgan_adam_multi_tensor / cgan_rmsprop_multi_tensor   if found_inf_device (may be NULL) holds a non-zero value nothing
+ *       is written.  Otherwise, with g' = g * inv_scale (+ weight_decay * p), g itself untouched:
+ *         Adam (amsgrad off):  m = b1 m + (1-b1) g' ; v = b2 v + (1-b2) g'^2
+ *                              p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
+ *         RMSprop (momentum 0, not centered):  v = alpha v + (1-alpha) g'^2 ; p -= lr * g' / (sqrt(v) + eps)
+ *       t = *step + 1 per tensor, read on the device; 1-b and the bias corrections are formed in double.
+ *   cgan_amp_optim_finish   *step += 1 for every item unless found_inf_device (may be NULL) holds a non-zero value.
+ * items_device: DEVICE array; all tensors fp32, contiguous; `step` a device scalar (fp32, as torch's capturable Adam
+ * keeps it); m is unused (may be NULL) for RMSprop and for the check.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+  float* p;
+  float* g;      /* written only by the check with write_back */
+  float* m;      /* exp_avg (Adam) */
+  float* v;      /* exp_avg_sq (Adam) / square_avg (RMSprop) */
+  float* step;   /* number of updates applied so far */
+  int64_t numel;
+} CganAmpOptimItem;
+int cgan_grads_nonfinite_check_multi_tensor(const CganAmpOptimItem* items_device, int32_t count, int64_t max_numel,
+                                            double inv_scale, int32_t write_back, float* found_inf_device, void* stream);
+int cgan_adam_multi_tensor(const CganAmpOptimItem* items_device, int32_t count, int64_t max_numel, double lr,
+                           double beta1, double beta2, double eps, double weight_decay, double inv_scale,
+                           const float* found_inf_device, void* stream);
+int cgan_rmsprop_multi_tensor(const CganAmpOptimItem* items_device, int32_t count, int64_t max_numel, double lr,
+                              double alpha, double eps, double weight_decay, double inv_scale,
+                              const float* found_inf_device, void* stream);
+int cgan_amp_optim_finish(const CganAmpOptimItem* items_device, int32_t count, const float* found_inf_device,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Edge / glue kernels
  * ------------------------------------------------------------------------------------------------ */
 /* fp32 NCHW [n][c][h][w] -> 16-bit NHWC [n][h][w][cs] (cs >= c, multiple of 4; pad channels zeroed).

@@ -3,7 +3,9 @@
               feature-matching + VGG losses;
 --tasks dsmp  the joint Masker + Painter step of BASELINE metric M1 (domains r, s, rf; --bs samples per domain).
 Also: --wgrad-table / --conv-table (per-shape tables of the conv calls of one step), --cprofile (host side),
---diff-aug (gen.p.diff_aug on with all three sub-options: the Painter discriminator's inputs augmented).
+--diff-aug (gen.p.diff_aug on with all three sub-options: the Painter discriminator's inputs augmented),
+--amp (train.amp: fp16 compute, Adam for G and D, one dynamic loss scaler per model -- to be set against the plain run's
+bf16 + ExtraAdam step on the same box; also prints the scales after the warm-up and at the end and the skipped steps).
 
 usage (GPU box): python tools/bench_train.py [--bs 8] [--steps 6] [--dtype bf16] [--no-vgg]
 """
@@ -175,6 +177,8 @@ def main():
     ap.add_argument("--no-vgg", action="store_true")
     ap.add_argument("--diff-aug", action="store_true",
                     help="gen.p.diff_aug.use with color jittering, translation and cutout on (defaults.yaml:158-164)")
+    ap.add_argument("--amp", action="store_true",
+                    help="train.amp: fp16 compute, optimizer Adam for G and D, dynamic loss scaling (the reference's AMP mode)")
     ap.add_argument("--tasks", default="p", help="'p' (Painter step) or 'dsmp' (joint Masker + Painter step: domains r, s, rf)")
     ap.add_argument("--conv-table", action="store_true", help="per-shape table of the forward / data-gradient conv calls of one step")
     ap.add_argument("--only", default="", choices=["", "G", "D"], help="time / profile only update_G or only update_D")
@@ -184,7 +188,7 @@ def main():
     ap.add_argument("--copy-trace", action="store_true", help="count the aten::copy_ / fill_ calls of one step by Python call site")
     ap.add_argument("--wgrad-table", action="store_true", help="per-shape table of the weight-gradient calls of one step")
     args = ap.parse_args()
-    dt = torch.float16 if args.dtype == "fp16" else torch.bfloat16
+    dt = torch.float16 if args.dtype == "fp16" or args.amp else torch.bfloat16
     if args.ddp_single:
         import os
         import torch.distributed as dist
@@ -200,6 +204,9 @@ def main():
         opts.train.lambdas.G.p.vgg = 0
     if args.diff_aug:
         opts.gen.p.diff_aug.update(use=True, do_color_jittering=True, do_translation=True, do_cutout=True)
+    if args.amp:
+        opts.train.amp = True
+        opts.gen.opt.optimizer = opts.dis.opt.optimizer = "Adam"
     T = Trainer(opts, device="cuda").setup(inference=False)
     for mod, seed in ((T.G, 0), (T.D, 1)):
         shapes = {k: tuple(v.shape) for k, v in mod.state_dict().items()}
@@ -222,6 +229,9 @@ def main():
     for _ in range(args.warmup):
         T.train_step(batch)
     torch.cuda.synchronize()
+    amp_warm = {"scale_G_after_warmup": T.grad_scaler_g.get_scale(), "scale_D_after_warmup": T.grad_scaler_d.get_scale(),
+                "skipped_G_in_warmup": T.grad_scaler_g.skipped_steps,
+                "skipped_D_in_warmup": T.grad_scaler_d.skipped_steps} if args.amp else {}
     if args.wgrad_table:
         return wgrad_table(T, batch)
     if args.conv_table:
@@ -266,10 +276,16 @@ def main():
         tg += b - a
         td += c - b
     dtot = time.perf_counter() - t0
+    if args.amp:
+        amp_warm.update(scale_G=T.grad_scaler_g.get_scale(), scale_D=T.grad_scaler_d.get_scale(),
+                        skipped_G=T.grad_scaler_g.skipped_steps, skipped_D=T.grad_scaler_d.skipped_steps,
+                        optimizer_steps_per_model=args.warmup + 1 + args.steps)
     print(json.dumps({
-        "workload": "%s train step (update_G + update_D, ExtraAdam), %dx%d bs %d per domain %s, vgg=%s%s" % (
-            "Painter" if args.tasks == "p" else "joint Masker+Painter (domains r, s, rf)", args.size, args.size, args.bs, args.dtype, not args.no_vgg,
-            ", diff_aug" if args.diff_aug else ""),
+        "workload": "%s train step (update_G + update_D, %s), %dx%d bs %d per domain %s, vgg=%s%s" % (
+            "Painter" if args.tasks == "p" else "joint Masker+Painter (domains r, s, rf)",
+            "train.amp: Adam + dynamic loss scale" if args.amp else "ExtraAdam", args.size, args.size, args.bs,
+            "fp16" if args.amp else args.dtype, not args.no_vgg, ", diff_aug" if args.diff_aug else ""),
+        **({"amp": amp_warm} if args.amp else {}),
         "images_per_s": round(args.bs * args.steps / dtot, 2), "raw_images_per_s": round(args.bs * len(batch) * args.steps / dtot, 2), "ms_per_step": round(dtot / args.steps * 1e3, 1),
         "host_enqueue_ms": round(enqueue_ms, 1), "gpu_drain_after_enqueue_ms": round(drain_ms, 1),
         "update_G_ms": round(tg / args.steps * 1e3, 1), "update_D_ms": round(td / args.steps * 1e3, 1),
