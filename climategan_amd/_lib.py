@@ -254,6 +254,9 @@ _SIGNATURES = {
     "cgan_normalize_u8_nhwc": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t,
                                          _P]),
     "cgan_binarize": (C.c_int, [_P, C.c_int32, _P, _P, C.c_float, C.c_int64, _P]),
+    "cgan_png_bound_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "cgan_png_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "cgan_png_encode_u8": (C.c_int, [_P] + [C.c_int32] * 4 + [_P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     "cgan_smog_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "cgan_smog_nchw": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), _P, C.c_size_t, _P]),

@@ -642,6 +642,46 @@ def binarize(x: torch.Tensor, threshold: float, want_float: bool = True, want_ui
     return y if want_float else y8
 
 
+PNG_MAX_WIDTH = 4096         # the widest row cgan_png_encode_u8 takes (pixels, grey or RGB)
+
+
+def png_bound_bytes(h: int, w: int, c: int) -> int:
+    """The most bytes the PNG file of one [h, w, c] image can have (``png_encode``'s row pitch)."""
+    bound = _lib.load().cgan_png_bound_bytes(int(h), int(w), int(c))
+    if bound == 0:
+        _lib.check(-1, "cgan_png_bound_bytes")
+    return bound
+
+
+def png_encode(img_u8: torch.Tensor):
+    """uint8 [N, H, W, C] device tensor (contiguous, C = 1 grey or 3 RGB, W <= PNG_MAX_WIDTH) -> (buf uint8 [N, bound],
+    sizes int64 [N]): ``buf[i, :sizes[i]]`` is the complete PNG file of image i.  Both stay on the device and
+    nothing is synchronised; everything else is refused here, before any launch."""
+    _need_cuda(img_u8)
+    if img_u8.dtype != torch.uint8:
+        raise RuntimeError("png_encode: uint8 input expected, got %s" % img_u8.dtype)
+    if img_u8.dim() != 4 or img_u8.shape[3] not in (1, 3):
+        raise RuntimeError("png_encode: [N, H, W, C] with C = 1 (grey) or 3 (RGB) expected, got %s" % (tuple(img_u8.shape),))
+    if not img_u8.is_contiguous():
+        raise RuntimeError("png_encode: a contiguous tensor is expected (strides %s)" % (img_u8.stride(),))
+    n, h, w, c = img_u8.shape
+    if w > PNG_MAX_WIDTH:
+        raise RuntimeError("png_encode: width %d exceeds the %d pixels per row the encoder supports" % (w, PNG_MAX_WIDTH))
+    if n < 1 or h < 1 or w < 1:
+        raise RuntimeError("png_encode: empty input %s" % (tuple(img_u8.shape),))
+    lib = _lib.load()
+    bound = png_bound_bytes(h, w, c)
+    nbytes = lib.cgan_png_workspace_bytes(n, h, w, c)
+    if nbytes == 0:
+        _lib.check(-1, "cgan_png_workspace_bytes")
+    ws = _empty(nbytes, dtype=torch.uint8, device=img_u8.device)
+    buf = _empty((n, bound), dtype=torch.uint8, device=img_u8.device)
+    sizes = _empty((n,), dtype=torch.int64, device=img_u8.device)
+    _lib.check(lib.cgan_png_encode_u8(_ptr(img_u8), n, h, w, c, _ptr(buf), bound, _ptr(sizes), _ptr(ws), nbytes, _stream()),
+               "cgan_png_encode_u8")
+    return buf, sizes
+
+
 def smog(x: torch.Tensor, depth: NHWC, airlight: float, beta: float, alpha: float, yellow_rgb01) -> torch.Tensor:
     """Smog event (reference trainer.py:1879-1939): x NCHW fp32 in [-1, 1], depth the decoder's 1-channel NHWC map;
     returns the smogged image, NCHW fp32."""

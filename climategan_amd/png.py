@@ -1,0 +1,48 @@
+"""PNG files from uint8 device images: ``ops.png_encode`` (csrc/png.hip) builds the files on the device, this
+module brings their bytes to the host and writes them.  There is no host encoder behind it: a CPU tensor is refused.
+
+Only the compressed bytes cross PCIe.  How many they are is known on the device alone, so a batch costs two waits: one for
+the N file lengths (8 N bytes; this is where the host waits for the encoder), one for a single copy of the first
+``max(lengths)`` bytes of every row of the output buffer into pinned memory.
+"""
+import torch
+
+from . import ops
+
+_PINNED = None
+
+
+def _pinned(nbytes):
+    """A pinned staging buffer, kept and grown between calls (pinning memory costs far more than the copy it serves)."""
+    global _PINNED
+    if _PINNED is None or _PINNED.numel() < nbytes:
+        _PINNED = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
+    return _PINNED[:nbytes]
+
+
+def _fetch(img_u8):
+    """-> (host uint8 array [N, max length] in the pinned buffer, list of N lengths); valid until the next call."""
+    buf, sizes = ops.png_encode(img_u8)
+    lengths = sizes.cpu().tolist()
+    n, longest = buf.shape[0], max(lengths)
+    host = _pinned(n * longest).view(n, longest)
+    host.copy_(buf[:, :longest], non_blocking=True)
+    torch.cuda.current_stream(img_u8.device).synchronize()
+    return host.numpy(), lengths
+
+
+def encode(img_u8):
+    """uint8 [N, H, W, C] device tensor (C = 1 or 3) -> list of N ``bytes``, each a complete PNG file."""
+    host, lengths = _fetch(img_u8)
+    return [host[i, :k].tobytes() for i, k in enumerate(lengths)]
+
+
+def write(img_u8, paths):
+    """Encode a batch on the device and write image i to ``paths[i]``."""
+    paths = list(paths)
+    if len(paths) != img_u8.shape[0]:
+        raise ValueError("png.write: %d images but %d paths" % (img_u8.shape[0], len(paths)))
+    host, lengths = _fetch(img_u8)
+    for i, (path, k) in enumerate(zip(paths, lengths)):
+        with open(path, "wb") as f:
+            f.write(memoryview(host[i, :k]))

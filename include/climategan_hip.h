@@ -633,6 +633,21 @@ int cgan_normalize_u8_nhwc(const void* x_nchw, int32_t is_half, uint8_t* out_nhw
  * `((mask > bin_value) * 255).astype(uint8)` (trainer.py:329-332) into y_u8 (may be NULL) */
 int cgan_binarize(const void* x, int32_t is_half, void* y, uint8_t* y_u8, float threshold, int64_t numel, void* stream);
 
+/* PNG files on the device (the "write" stage of apply_events.py:580-620 up to the file's bytes).
+ * in: uint8 [n][h][w][c], c = 1 (grey) or 3 (RGB), 1 <= w <= 4096, 1 <= n <= 65535 -> out + i * out_pitch: a complete PNG
+ * file of image i (signature, IHDR, one IDAT per row, a closing IDAT, IEND; per-row filter choice by the minimum sum of
+ * absolute values over None / Sub / Up / Average / Paeth; fixed-Huffman deflate with literals and matches at distance 1 and
+ * c inside the row; every CRC-32 and the Adler-32 computed on the device), sizes[i]: its length in bytes.  The bytes of
+ * out behind sizes[i] are left as they were.  A file never exceeds the bound
+ *   65 + h * (12 + ceil((9 * (w * c + 1) + 13) / 8) + 4) bytes,
+ * out_pitch must be at least that; the workspace (16-byte aligned) holds one staging slot per row.  The bytes of a file
+ * depend on its image alone: not on the batch, not on the run.  The two size queries return 0 (and set the error text) for
+ * a shape the encoder refuses. */
+size_t cgan_png_bound_bytes(int32_t h, int32_t w, int32_t c);
+size_t cgan_png_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c);
+int cgan_png_encode_u8(const uint8_t* in, int32_t n, int32_t h, int32_t w, int32_t c, uint8_t* out, size_t out_pitch,
+                       int64_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Smog event (Trainer.compute_smog, climategan/trainer.py:1879-1939, parameters shared/trainer/events.yaml:9-14):
  * irradiance = srgb2lrgb(normalize(x)) (tutils.py:534-538), depth = normalize(1 / normalize(d, 0.3, 1), 0.1, 1)
  * bilinearly resized (align_corners=True) to (h, w), transmission = exp(-beta depth),
