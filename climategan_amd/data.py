@@ -11,15 +11,24 @@ array for the 8-bit RGB / RGBA / grey and the 16-bit grey PNGs the datasets hold
 ``classes_dict`` and ``kitti_mapping`` restate the reference's tables as data; tests/golden/data_decode.npz records the
 reference's own and the host test compares.
 
-Out of scope: ``OmniListDataset`` / ``get_loader`` and the Logger's display helpers (``decode_segmap_merged_labels``, ...).
+**The loaders** (``data.py:402-539``): ``OmniListDataset`` reads the file lists; ``get_loader`` returns an
+``OmniLoader`` -- an iterable of collated batches, not a ``torch.utils.data.DataLoader``: its workers are THREADS that read
+and decode files into numpy arrays, one batch ahead of the consumer; the arrays of a task travel through one pinned
+buffer and one copy on a side stream, and the whole batch is then the one launch per task of ``compile_transforms``.
+
+Out of scope: the Logger's display helpers (``decode_segmap_merged_labels``, ...).
 """
+import json
+import time
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import numpy as np
 import torch
 
 from . import ops
-from .transforms import RawSource
+from .transforms import Compose, RawSource, compile_transforms, get_transforms, set_draws
+from .utils import env_to_path
 
 classes_dict = {
     "s": {0: [0, 0, 255, 255], 1: [55, 55, 55, 255], 2: [0, 255, 255, 255], 3: [255, 212, 0, 255], 4: [0, 255, 0, 255],
@@ -150,3 +159,347 @@ def tensor_loader(source, task, domain, opts, device=None):
     if task == "s" and domain != "kitti" and isinstance(source, (str, Path)) and Path(source).suffix == ".pt":
         return torch.load(source)
     return raw_source(source, task, domain, opts, device).to_tensor()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The datasets and loaders (reference data.py:402-539)
+# ----------------------------------------------------------------------------------------------------------------------
+MAX_WORKERS = 16        # reader threads of one loader, whatever the machine's CPU count
+
+
+def read_host(path, task, domain):
+    """The host half of ``raw_source``: ``(array, known)`` with the contiguous numpy array the device half wraps (the
+    fourth channel of ``x`` and ``m`` dropped, the real domain's depth as fp32: data.py:364, 382-383) and what a pass over
+    the array tells while it is in the cache -- ``minmax`` of ``x`` and of the real depth, the mask's ``threshold`` --
+    so that no launch has to find them.  A ``.pt`` segmentation map is returned as the tensor ``torch.load`` gives."""
+    path = Path(path)
+    if task == "s" and domain != "kitti" and path.suffix == ".pt":
+        return torch.load(path), {}
+    arr = read_array(path)
+    known = {}
+    if task in ("x", "m") and arr.ndim == 3 and arr.shape[-1] == 4:
+        arr = arr[:, :, :3]
+    if task == "d" and domain == "r":
+        arr = arr.astype(np.float32, copy=False)
+    arr = np.ascontiguousarray(arr)
+    if task == "x" or (task == "d" and domain == "r"):
+        known["minmax"] = (arr.min(), arr.max())
+    elif task == "m":
+        known["threshold"] = bool(arr.max() > 127)
+    return arr, known
+
+
+class OmniListDataset:
+    """reference data.py:402-504: the samples of one ``opts.data.files[mode][domain]`` list (``.json`` or ``.yaml``; a
+    name without ``/`` is looked up in ``opts.data.files.base``), cut to ``opts.data.max_samples``, each reduced to the
+    tasks of ``opts.tasks`` (+ ``x``, + ``m`` with the Painter).  ``dataset[i]`` is the reference's item through the
+    per-sample path (``tensor_loader`` + ``Compose(get_transforms(...))``); ``read_raw(i)`` gives the sample as the
+    ``RawSource``s the batch transform reads."""
+
+    def __init__(self, mode, domain, opts, transform=None, device=None):
+        import yaml
+
+        self.opts, self.domain, self.mode, self.device = opts, domain, mode, device
+        self.tasks = set(opts.tasks)
+        self.tasks.add("x")
+        if "p" in self.tasks:
+            self.tasks.add("m")
+        file_list_path = list_path(opts, mode, domain)
+        with open(file_list_path, "r") as f:
+            if file_list_path.suffix == ".json":
+                self.samples_paths = json.load(f)
+            elif file_list_path.suffix in {".yaml", ".yml"}:
+                self.samples_paths = yaml.safe_load(f)
+            else:
+                raise ValueError("Unknown file list type in {}".format(file_list_path))
+        max_samples = opts.data.get("max_samples")
+        if max_samples and max_samples != -1:
+            assert isinstance(max_samples, int)
+            self.samples_paths = self.samples_paths[:max_samples]
+        self.filter_samples()
+        if opts.data.get("check_samples"):
+            print(f"Checking samples ({mode}, {domain})")
+            self.check_samples()
+        self.file_list_path = str(file_list_path)
+        self.transform = transform if transform is not None else Compose(get_transforms(opts, mode, domain))
+
+    def filter_samples(self):
+        """data.py:437-444: only the files of the model's tasks"""
+        self.samples_paths = [{k: v for k, v in s.items() if k in self.tasks} for s in self.samples_paths]
+
+    def check_samples(self):
+        """data.py:497-503: every listed file exists"""
+        for s in self.samples_paths:
+            for k, v in s.items():
+                assert Path(v).exists(), f"{k} {v} does not exist"
+
+    def __len__(self):
+        return len(self.samples_paths)
+
+    def __getitem__(self, i):
+        paths = self.samples_paths[i]
+        data = {task: tensor_loader(env_to_path(path), task, self.domain, self.opts, self.device)
+                for task, path in paths.items()}
+        return {"data": self.transform(data), "paths": paths, "domain": self.domain if self.domain != "kitti" else "s",
+                "mode": self.mode}
+
+    def read_host(self, i):
+        """{task: (array, known)} of sample ``i``: the part of ``read_raw`` that runs in a reader thread"""
+        return {task: read_host(env_to_path(path), task, self.domain) for task, path in self.samples_paths[i].items()}
+
+    def wrap(self, task, array, known=None):
+        """The ``RawSource`` of a device array of this dataset's ``task`` (a ``.pt`` map stays the tensor it is)"""
+        if array.is_floating_point() and array.dim() == 4:
+            return array
+        return raw_source(array, task, self.domain, self.opts).set_known(**(known or {}))
+
+    def read_raw(self, i, device=None):
+        """{task: RawSource} of sample ``i`` on the device: the file through ``read_array`` on the host, the array as it is
+        to the device; the decode happens in the gather that reads it"""
+        dev = _device(device if device is not None else self.device)
+        return {task: self.wrap(task, (v if torch.is_tensor(v) else torch.from_numpy(v)).to(dev), known)
+                for task, (v, known) in self.read_host(i).items()}
+
+
+class _Slot:
+    """One batch in flight: per task a pinned staging buffer and its device copy, the event recorded behind the upload
+    and the event recorded behind the gather that read the device copy"""
+
+    ALIGN = 256         # every sample starts on a boundary the 16-byte loads of the min / max kernels accept
+
+    def __init__(self):
+        self.pinned, self.dev = {}, {}
+        self.uploaded = self.consumed = None
+
+    def buffers(self, task, nbytes, device):
+        if task not in self.pinned or self.pinned[task].numel() < nbytes:
+            size = max(nbytes + nbytes // 4, 1 << 16)
+            self.pinned[task] = torch.empty(size, dtype=torch.uint8).pin_memory()
+            self.dev[task] = torch.empty(size, dtype=torch.uint8, device=device)
+        return self.pinned[task], self.dev[task]
+
+
+class OmniLoader:
+    """What ``get_loader`` returns: an iterable of the reference's collated batches ``{"data": {task: [N, C, h, w] device
+    tensor}, "paths": {task: [path] * N}, "domain": [domain] * N, "mode": [mode] * N}`` with ``len()``, ``.dataset`` and
+    ``.batch_size``; ``drop_last`` and ``shuffle`` as the reference sets them (data.py:516-528).
+
+    Every ``__iter__`` draws a fresh permutation from ``self.generator``, a ``torch.Generator`` of the loader's own whose
+    first seed comes from torch's default generator (so ``torch.manual_seed`` before ``get_loader`` fixes the epochs, as it
+    fixes ``transforms.TorchDraws``); ``seed(n)`` sets it.  A batch is ``num_workers`` threads reading the files
+    (``dataset.read_host``), one pinned buffer and one copy per task, then ``compile_transforms`` on the list of raw
+    samples: the transform draws are made on the consumer's thread in sample order, so a batch depends on the
+    permutation and on the draws alone.
+
+    ``prefetch=1``: batch k + 1 is read and uploaded on a side stream while the consumer works on batch k; the consumer's
+    stream waits for the upload's event before the gather, and the side stream for the gather's event before it writes
+    the buffers again.  ``prefetch=0``: no thread and no second stream, everything in ``__iter__`` on the current stream.
+    There are no worker processes: each would open the GPU."""
+
+    def __init__(self, dataset, batch_size, num_workers=0, prefetch=1, shuffle=True, device=None, transform=None):
+        self.dataset, self.batch_size = dataset, int(batch_size)
+        self.num_workers = max(0, min(int(num_workers), MAX_WORKERS))
+        self.prefetch, self.shuffle = int(bool(prefetch)), shuffle
+        self.device = torch.device(device) if device is not None else _device(dataset.device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.transform = transform if transform is not None else compile_transforms(dataset.opts, dataset.mode, dataset.domain)
+        self.generator = torch.Generator()
+        self.generator.manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+        self.last_order = None
+        self.times = {"read": 0.0, "stage": 0.0, "transform": 0.0, "batches": 0}     # host seconds, summed
+        self._slots = [_Slot(), _Slot()]
+        self._pool = self._coord = self._side = self._pending = None
+
+    def seed(self, n):
+        self.generator.manual_seed(int(n))
+        return self
+
+    def set_draws(self, draws):
+        """The source of the transform draws of the batch path (default: the reference's numpy / random calls)"""
+        set_draws(self.transform.transforms, draws)
+        return self
+
+    def __len__(self):
+        return len(self.dataset) // self.batch_size
+
+    # -------------------------------------------------------------------------------------------- the producer's half
+    def _read(self, indices):
+        t0 = time.perf_counter()
+        if self._pool is not None:
+            samples = list(self._pool.map(self.dataset.read_host, indices))
+        else:
+            samples = [self.dataset.read_host(i) for i in indices]
+        self.times["read"] += time.perf_counter() - t0
+        return samples
+
+    def _stage(self, samples, slot, stream):
+        """The arrays of every task into the slot's pinned buffer, one copy per task on ``stream``; returns per sample
+        {task: (device array, known)}"""
+        t0 = time.perf_counter()
+        if slot.uploaded is not None:
+            slot.uploaded.synchronize()                 # the copy that last read the pinned buffers has run
+        staged = [{} for _ in samples]
+        with torch.cuda.stream(stream):
+            if slot.consumed is not None:
+                stream.wait_event(slot.consumed)        # the gather that last read the device buffers has run
+            for task in samples[0]:
+                arrays = [s[task][0] for s in samples]
+                offsets, total = [], 0
+                for a in arrays:
+                    offsets.append(total)
+                    if not torch.is_tensor(a):
+                        total += (a.nbytes + _Slot.ALIGN - 1) // _Slot.ALIGN * _Slot.ALIGN
+                pinned, dev = slot.buffers(task, total, self.device)
+                host = pinned.numpy()
+                for a, off in zip(arrays, offsets):
+                    if not torch.is_tensor(a):
+                        host[off:off + a.nbytes] = a.reshape(-1).view(np.uint8)
+                if total:
+                    dev[:total].copy_(pinned[:total], non_blocking=True)
+                for k, (a, off) in enumerate(zip(arrays, offsets)):
+                    if torch.is_tensor(a):
+                        t = a.to(self.device)
+                    else:
+                        t = dev[off:off + a.nbytes].view(torch.from_numpy(a[:0]).dtype).view(a.shape)
+                    staged[k][task] = (t, samples[k][task][1])
+            slot.uploaded = torch.cuda.Event()
+            slot.uploaded.record(stream)
+        self.times["stage"] += time.perf_counter() - t0
+        return staged
+
+    def _prepare(self, indices, slot):
+        """(reader threads ->) pinned buffers -> device, on the side stream; runs in the coordinator thread"""
+        torch.cuda.set_device(self.device)
+        return self._stage(self._read(indices), slot, self._side)
+
+    def _start(self):
+        if self._coord is None:
+            self._coord = ThreadPoolExecutor(max_workers=1, thread_name_prefix="omni-stage")
+            if self.num_workers > 0:
+                self._pool = ThreadPoolExecutor(max_workers=self.num_workers, thread_name_prefix="omni-read")
+            self._side = torch.cuda.Stream(device=self.device)
+
+    def _drain(self):
+        """Wait for a batch that an abandoned iteration left in flight (its slot is written by another thread)"""
+        pending, self._pending = self._pending, None
+        if pending is not None:
+            try:
+                pending.result()
+            except Exception:           # nobody asked for that batch
+                pass
+
+    def close(self):
+        """Stop the threads (a later ``__iter__`` starts them again)"""
+        self._drain()
+        for pool in (self._coord, self._pool):
+            if pool is not None:
+                pool.shutdown(wait=True)
+        self._coord = self._pool = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -------------------------------------------------------------------------------------------- the consumer's half
+    def collate(self, indices, data):
+        """The reference's default collate of the per-sample items (data.py:467-482)"""
+        paths = [self.dataset.samples_paths[i] for i in indices]
+        domain = self.dataset.domain if self.dataset.domain != "kitti" else "s"
+        return {"data": data, "paths": {task: [p[task] for p in paths] for task in paths[0]},
+                "domain": [domain] * len(indices), "mode": [self.dataset.mode] * len(indices)}
+
+    def _finish(self, indices, staged, slot):
+        t0 = time.perf_counter()
+        stream = torch.cuda.current_stream(self.device)
+        stream.wait_event(slot.uploaded)
+        samples = [{task: self.dataset.wrap(task, t, known) for task, (t, known) in s.items()} for s in staged]
+        data = self.transform(samples)
+        slot.consumed = torch.cuda.Event()
+        slot.consumed.record(stream)
+        self.times["transform"] += time.perf_counter() - t0
+        self.times["batches"] += 1
+        return self.collate(indices, data)
+
+    def batches(self):
+        """The index lists of one epoch: a fresh permutation, cut into full batches"""
+        n = len(self.dataset)
+        order = torch.randperm(n, generator=self.generator).tolist() if self.shuffle else list(range(n))
+        self.last_order = order
+        return [order[k * self.batch_size:(k + 1) * self.batch_size] for k in range(len(self))]
+
+    def __iter__(self):
+        self._drain()
+        batches = self.batches()
+        if self.device.type != "cuda":
+            # nothing is staged: the host arrays go to ``transform`` as they are.  The kernels have no CPU path, so this
+            # serves a caller's own transform only (the tests of the bookkeeping)
+            for indices in batches:
+                yield self.collate(indices, self.transform([{t: v[0] for t, v in s.items()} for s in self._read(indices)]))
+            return
+        if not self.prefetch:
+            slot = self._slots[0]
+            for indices in batches:
+                yield self._finish(indices, self._stage(self._read(indices), slot, torch.cuda.current_stream(self.device)), slot)
+            return
+        self._start()
+        if batches:
+            self._pending = self._coord.submit(self._prepare, batches[0], self._slots[0])
+        for k, indices in enumerate(batches):
+            staged = self._pending.result()
+            self._pending = None
+            if k + 1 < len(batches):        # the next batch is read and uploaded while this one is transformed and used
+                self._pending = self._coord.submit(self._prepare, batches[k + 1], self._slots[(k + 1) % 2])
+            yield self._finish(indices, staged, self._slots[k % 2])
+
+
+def get_loader(mode, domain, opts, prefetch=1, device=None):
+    """reference data.py:506-528: the loader of one mode and domain; ``opts.data.loaders.batch_size`` samples per batch
+    (``opts.train.kitti.batch_size`` for the kitti domain while ``train.kitti.pretrain``), shuffled, the last partial batch
+    dropped, ``min(opts.data.loaders.num_workers, 16)`` reader threads."""
+    loaders = opts.data.get("loaders") or {}
+    kitti = opts.train.get("kitti") or {}
+    if domain != "kitti" or not kitti.get("pretrain") or not kitti.get("batch_size"):
+        batch_size = loaders.get("batch_size", 4)
+    else:
+        batch_size = kitti.get("batch_size", 4)
+    return OmniLoader(OmniListDataset(mode, domain, opts, device=device), batch_size,
+                      num_workers=loaders.get("num_workers", 8), prefetch=prefetch, device=device)
+
+
+def loader_domains(opts):
+    """The domains the tasks read, as the reference's ``load_opts`` sets ``opts.domains`` (utils.py:164-172): r and s for
+    the Masker's tasks, rf for the Painter; kitti whenever it is listed (``Trainer.loaders`` leaves it out)"""
+    if opts.get("domains"):
+        return list(opts.domains)
+    domains = ["r", "s"] if any(t in opts.tasks for t in "msd") else []
+    if "p" in opts.tasks:
+        domains.append("rf")
+    return domains + ["kitti"]
+
+
+def list_path(opts, mode, domain):
+    """data.py:413-417: the file list of a mode and domain; a name without ``/`` lies in ``opts.data.files.base``"""
+    path = Path(opts.data.files[mode][domain])
+    return path if "/" in str(path) else Path(opts.data.files.base) / path
+
+
+def listed_files(opts):
+    """The file lists ``get_all_loaders`` would read, existing or not"""
+    files = (opts.get("data") or {}).get("files") or {}
+    return [list_path(opts, mode, domain) for mode in ("train", "val") if mode in files
+            for domain in loader_domains(opts) if domain in files[mode]]
+
+
+def get_all_loaders(opts, prefetch=1, device=None):
+    """reference data.py:531-539: ``{mode: {domain: loader}}`` for the modes and domains listed in ``opts.data.files``"""
+    loaders = {}
+    for mode in ["train", "val"]:
+        loaders[mode] = {}
+        if mode in opts.data.files:
+            for domain in loader_domains(opts):
+                if domain in opts.data.files[mode]:
+                    loaders[mode][domain] = get_loader(mode, domain, opts, prefetch, device)
+    return loaders

@@ -11,6 +11,11 @@ schedulers (``get_optimizer``); ``update_G`` / ``update_D`` / ``train_step`` rep
 (trainer.py:1184-1254, 1389-1616), ``get_painter_loss`` (trainer.py:1256-1387), ``get_D_loss`` (trainer.py:1034-1160)
 and the extrapolate / step schedule (trainer.py:674-694); ``save`` / ``resume`` / ``update_learning_rates`` are the
 checkpoint half (trainer.py:396-579): same file layout, same path rules.
+
+The loop (trainer.py:626-643, 848-987): with ``opts.data.files`` present ``setup()`` builds the loaders
+(``data.get_all_loaders``) and the display images; ``run_epoch()`` / ``run_evaluation()`` without arguments read them and
+``train()`` is the reference's epoch loop.  Kitti pre-training and pseudo-label training have no path here and are refused
+by ``setup()``.
 """
 import os
 import time
@@ -61,7 +66,8 @@ def _merge(source, destination):
 
 
 class Trainer:
-    """Inference-side subset of the reference Trainer (trainer.py:63-216): owns ``G``; no logger / comet / data."""
+    """The reference Trainer (trainer.py:63-216) without its logger and comet experiment: owns ``G``, ``D``, the optimizers
+    and, with ``opts.data.files``, the loaders."""
 
     def __init__(self, opts, comet_exp=None, verbose=0, device=None):
         self.opts = opts
@@ -99,6 +105,8 @@ class Trainer:
 
     def setup(self, inference=False):
         """reference trainer.py:701-789."""
+        if not inference:
+            self._refuse_unbuilt_training_options()
         self.G = create_generator(self.opts, device=self.device, no_init=inference, verbose=self.verbose)
         # trainer.py:725: a generator without its own Painter may borrow a validation-only one (opts.val.val_painter)
         own_painter = sum(p.numel() for p in self.G.painter.parameters()) > 0
@@ -153,10 +161,82 @@ class Trainer:
             broadcast_parameters(self.D)
             self.g_reducer = GradBucketReducer(g_params)
             self.d_reducer = GradBucketReducer(d_params)
+        # the data (trainer.py:713, 787, 800): built last, so that the models are initialised from the same generator
+        # state with and without it
+        self.all_loaders = self.loaders = None
+        from .data import listed_files
+        if any(path.exists() for path in listed_files(o)):
+            # (options that came with a checkpoint from another machine name lists that are not here: such a trainer is
+            # set up without data, as before, and run_epoch() / train() without batches say so)
+            from .data import get_all_loaders
+            self.all_loaders = get_all_loaders(o, device=self.device)
+            if self.verbose > 0:
+                for mode, mode_dict in self.all_loaders.items():
+                    for domain, loader in mode_dict.items():
+                        print("Loader {} {} : {}".format(mode, domain, len(loader.dataset)))
+            # switch_data(to="base"), trainer.py:828-838: every domain but kitti
+            self.loaders = {mode: {domain: loader for domain, loader in mode_dict.items() if domain != "kitti"}
+                            for mode, mode_dict in self.all_loaders.items()}
+            self.set_display_images()
         if os.environ.get("CGAN_GC_FREEZE", "0") == "1":
             self.freeze_host_objects()
         self.is_setup = True
         return self
+
+    def _refuse_unbuilt_training_options(self):
+        """The two training schedules of the reference's ``train`` loop that have no path here (trainer.py:797-800,
+        915-922): refused by name instead of training something else."""
+        train = self.opts.get("train") or {}
+        if (train.get("kitti") or {}).get("pretrain"):
+            raise NotImplementedError("train.kitti.pretrain: the trainer has no kitti pre-training path (no data switch, no "
+                                      "frozen discriminator update); set train.kitti.pretrain to false")
+        pseudo = train.get("pseudo") or {}
+        epochs = pseudo.get("epochs") or 0
+        if pseudo.get("tasks") and (epochs > 0 or epochs == -1):
+            raise NotImplementedError("train.pseudo.tasks = %s with train.pseudo.epochs = %s: the trainer has no pseudo-label "
+                                      "path (losses on the real domain's pseudo labels); leave train.pseudo.tasks empty"
+                                      % (list(pseudo.get("tasks")), epochs))
+
+    @property
+    def train_loaders(self):
+        """reference trainer.py:626-633: a zip of the training loaders, in the dict's order"""
+        return zip(*list(self._loaders_of("train").values()))
+
+    @property
+    def val_loaders(self):
+        """reference trainer.py:635-643"""
+        return zip(*list(self._loaders_of("val").values()))
+
+    def _loaders_of(self, mode):
+        if not getattr(self, "loaders", None) or not self.loaders.get(mode):
+            raise ValueError("Trainer: no %s loaders -- set opts.data.files.%s before setup(), or hand the batches to "
+                             "run_epoch / run_evaluation" % (mode, mode))
+        return self.loaders[mode]
+
+    @staticmethod
+    def _multi_domain_batches(zipped, shuffle):
+        """trainer.py:939-954, 1660-1668: per iteration the tuple of domain batches keyed by domain (the ``[0]``: a collated
+        batch holds its domain once per sample); the training loop shuffles the tuple first, the validation does not"""
+        from .tutils import shuffle_batch_tuple
+        for multi_batch_tuple in zipped:
+            if shuffle:
+                multi_batch_tuple = shuffle_batch_tuple(multi_batch_tuple)
+            yield {batch["domain"][0]: batch for batch in multi_batch_tuple}
+
+    def set_display_images(self, use_all=False):
+        """reference trainer.py:848-886: ``self.display_images[mode][domain]`` = the dataset items (per-sample path) at
+        ``get_display_indices`` -- or all of them -- for every domain but kitti: what ``eval_images`` reads"""
+        from .utils import get_display_indices
+
+        self.display_images = {}
+        for mode, mode_dict in self.all_loaders.items():
+            self.display_images[mode] = {}
+            for domain, loader in mode_dict.items():
+                if domain == "kitti":
+                    continue
+                dataset = loader.dataset
+                indices = list(range(len(dataset))) if use_all else get_display_indices(self.opts, domain, len(dataset))
+                self.display_images[mode][domain] = [dataset[int(i)] for i in indices if i < len(dataset)]
 
     def freeze_host_objects(self):
         """Opt-in, for a process that trains ONE trainer for its whole life (bench.py, a training entry point; or
@@ -819,11 +899,14 @@ class Trainer:
             self.use_pl4m = True
         return self.use_pl4m
 
-    def run_epoch(self, batches):
+    def run_epoch(self, batches=None):
         """One epoch of the reference's loop (``train``'s pl4m check trainer.py:899-909, then ``run_epoch`` trainer.py:924-987)
-        over an iterable of multi-domain batches (the zipped loaders are the caller's: data loading is out of scope):
-        per batch ``update_G`` + ``update_D`` + step counter; per epoch the learning-rate schedulers and the epoch
-        counter.  Returns the last (g_loss, d_loss)."""
+        over an iterable of multi-domain batches: per batch ``update_G`` + ``update_D`` + step counter; per epoch the
+        learning-rate schedulers and the epoch counter.  Without ``batches``: train mode, then the zipped training loaders,
+        each tuple shuffled and keyed by domain (trainer.py:932-954).  Returns the last (g_loss, d_loss)."""
+        if batches is None:
+            self.train_mode()
+            batches = self._multi_domain_batches(self.train_loaders, True)
         self.maybe_enable_pl4m()
         last = None
         for multi_domain_batch in batches:
@@ -831,6 +914,23 @@ class Trainer:
         self.update_learning_rates()                                    # trainer.py:983-984
         self.epoch += 1
         return last
+
+    def train(self):
+        """reference trainer.py:888-922: for ``opts.train.epochs`` epochs ``run_epoch()``, ``run_evaluation()``, ``save()``
+        (the pl4m check is ``run_epoch``'s; the kitti and pseudo-label switches are refused by ``setup``).  ``run_epoch``
+        has counted the epoch when ``save`` runs: a checkpoint's ``epoch`` is the number of finished epochs.  One line per
+        epoch; returns the list of ``run_evaluation``'s results."""
+        assert self.is_setup
+        results = []
+        for _ in range(int(self.opts.train.epochs)):
+            start, step = time.perf_counter(), self.global_step
+            last = self.run_epoch()
+            results.append(self.run_evaluation())
+            self.save()
+            g, d = (float(last[0]), float(last[1])) if last is not None else (float("nan"), float("nan"))
+            print("epoch %d: %d steps in %.1f s, last G loss %.4f, last D loss %.4f"
+                  % (self.epoch - 1, self.global_step - step, time.perf_counter() - start, g, d))
+        return results
 
     # ------------------------------------------------------------------------------------------ validation
     def eval_mode(self):
@@ -862,12 +962,14 @@ class Trainer:
         return g_loss
 
     @torch.no_grad()
-    def run_evaluation(self, val_batches, display_images=None):
-        """reference trainer.py:1653-1704 over an iterable of multi-domain validation batches (the zipped loaders are the
-        caller's): eval mode, ``get_G_loss`` per batch with the logged generator terms AVERAGED over the batches
-        (sum_dict / div_dict, trainer.py:1674-1679), then ``eval_images("val", d)`` for d in r, s when the Masker has an
+    def run_evaluation(self, val_batches=None, display_images=None):
+        """reference trainer.py:1653-1704 over an iterable of multi-domain validation batches (without one: the zipped
+        validation loaders, each tuple keyed by domain): eval mode, ``get_G_loss`` per batch with the logged generator terms
+        AVERAGED over the batches (sum_dict / div_dict, trainer.py:1674-1679), then ``eval_images("val", d)`` for d in r, s when the Masker has an
         m or s task, train mode again.  Comet image panels and the validation FID (logger.py, fid.py) are outside this
         path.  Returns {"losses": averaged terms, "metrics": {domain: eval_images' table}}."""
+        if val_batches is None:
+            val_batches = self._multi_domain_batches(self.val_loaders, False)
         self.eval_mode()
         sums, n = {}, 0
         for multi_domain_batch in val_batches:

@@ -380,12 +380,20 @@ class RawSource:
         self.t, self.kind, self.code, self.palette = arr, kind, code, palette
         self.far, self.log = float(far), bool(log)
         self.normalize = bool(normalize) or kind == "f32_d"
-        self.threshold = None if threshold is None else bool(threshold)
+        self.threshold = None
         self.min = self.range = None
+        self.set_known(minmax, threshold)
+
+    def set_known(self, minmax=None, threshold=None):
+        """What the caller knows of the whole source, so that no launch has to look for it: ``minmax`` and, for a mask,
+        ``threshold`` (see the class docstring); None leaves a value as it is."""
+        if threshold is not None:
+            self.threshold = bool(threshold)
         if minmax is not None:
             # ``t - min`` then ``/ max(t - min)``: the divisor is the fp32 difference
             self.min = float(np.float32(minmax[0]))
             self.range = float(np.float32(minmax[1]) - np.float32(minmax[0]))
+        return self
 
     @classmethod
     def from_numpy(cls, arr, kind, device, **kw):

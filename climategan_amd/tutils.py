@@ -158,3 +158,12 @@ def decode_unity_depth_t(unity_depth, log=True, normalize=False, numpy=False, fa
     if numpy:
         return depth.data.cpu().numpy().astype(np.uint8).squeeze()
     return depth
+
+
+def shuffle_batch_tuple(mbt):
+    """reference tutils.py:316-328: the domain batches of one iteration in a random order (``np.random.permutation`` on the
+    global numpy generator); only the order of the tuple changes."""
+    assert isinstance(mbt, (tuple, list))
+    assert len(mbt) > 0
+    perm = np.random.permutation(len(mbt))
+    return [mbt[i] for i in perm]

@@ -39,3 +39,40 @@ def flatten_opts(opts) -> dict:
 
     walk(opts, "")
     return out
+
+
+def env_to_path(path):
+    """reference utils.py:367-382: every ``/``-separated part of ``path`` that holds a ``$`` becomes the value of that
+    environment variable (``$HOME/clouds`` -> ``/home/me/clouds``); a variable that is not set is a KeyError."""
+    import os
+
+    return "/".join(os.environ[el.replace("$", "")] if "$" in el else el for el in str(path).split("/"))
+
+
+def get_display_indices(opts, domain, length):
+    """reference utils.py:669-713: the dataset indices of the display images.  ``opts.comet.display_size`` as an int n gives
+    the first n entries of ``np.random.permutation(length)`` under the temporary numpy seed 123 (the global numpy state
+    is left as it was); for ``rf`` n is at least ``train.fid.n_images``.  A list is returned as it is."""
+    import numpy as np
+
+    if domain == "rf":
+        dsize = max([opts.comet.display_size, opts.train.fid.get("n_images", 0)])
+    else:
+        dsize = opts.comet.display_size
+    assert isinstance(dsize, (int, list)) and not isinstance(dsize, dict), "Unknown display size {}".format(dsize)
+    if isinstance(dsize, list):
+        display_indices = list(dsize)
+    else:
+        if dsize > length:
+            print("Warning: dataset is smaller ({} images) than required display indices ({}). Selecting {} images."
+                  .format(length, dsize, length))
+        assert dsize >= 0, "Display size cannot be < 0"
+        state = np.random.get_state()                                   # temp_np_seed, utils.py:648-666
+        np.random.seed(123)
+        try:
+            display_indices = list(np.random.permutation(length)[:dsize])
+        finally:
+            np.random.set_state(state)
+    if not display_indices:
+        print("Warning: no display indices (utils.get_display_indices)")
+    return display_indices
