@@ -618,13 +618,13 @@ __global__ __launch_bounds__(64 * G * G, G == 4 ? 1 : (CH == 64 ? 2 : 4)) void c
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Spatially tiled variant for 3 x 3 / stride 1 / pad 1 layers on large maps (the SPADE gamma|beta gradients: 128 hidden
-// channels at 160^2 ... 640^2).  The kernels above treat every tap as its own N tile, so each tap's workgroups stream
-// their own shifted copy of x through L2 -> LDS: 9 x 419 MB of the 6.2 GB a 128 -> 40 call at 4 x 640^2 moved.  Here a
-// workgroup owns a (64 co) x (64 ci x 9 taps) block of dW -- 36 accumulator tiles per wave -- and walks 4 x 32 pixel
-// tiles: per tile it stages the dy tile (128 px) and the x tile WITH ITS HALO (6 rows x 40 px) once, and all nine taps
-// read their shifted windows from that one copy (the transposing LDS read takes a row address per lane, so a shifted
-// window costs nothing): 46 DMA pieces per 576 MFMAs instead of 8 per 32.
+// Spatially tiled variant for 3 x 3 / stride 1 / pad 1 layers on large maps.  (Written for the SPADE gamma|beta
+// gradients, which conv_wgrad_col3x3_kernel below has taken over; wgrad_plan names the layers that still run here.)
+// The kernels above treat every tap as its own N tile, so each tap's workgroups stream their own shifted copy of x
+// through L2 -> LDS.  Here a workgroup owns a (64 co) x (64 ci x 9 taps) block of dW -- 36 accumulator tiles per wave --
+// and walks 4 x 32 pixel tiles: per tile it stages the dy tile (128 px) and the x tile WITH ITS HALO (6 rows x 40 px)
+// once, and all nine taps read their shifted windows from that one copy (the transposing LDS read takes a row address
+// per lane, so a shifted window costs nothing): 46 DMA pieces per 576 MFMAs instead of 8 per 32.
 // wave w owns N tiles 9w .. 9w+8 of the 36 (N tile j = tap j / 4, 16-channel group j % 4).
 constexpr int TL_W = 32, TL_H = 4, TL_XP = 40;                 // pixel tile, LDS pitch (pixels) of a halo row
 constexpr int TL_XH_BYTES = (TL_H + 2) * TL_XP * 128;           // 30720
@@ -751,6 +751,218 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile3x3_kernel(WgradArgs p)
     f32x4* wst = reinterpret_cast<f32x4*>(p.ws) + ((size_t)split * tiles_n + tile) * 1024;
 #pragma unroll
     for (int a = 0; a < 4; ++a) wst[(a * 4 + grp) * 64 + lane] = a < NA ? acc[a < NA ? a : 0][i] : (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Column-walking variant of the spatially tiled kernel for cin_s = 64 / 128 (the SPADE gamma|beta gradients).  The tile
+// kernel above gives a workgroup one 64 co x 64 ci block, so the x halo tile is staged once per co block, the dy tile once
+// per ci block, every tile waits for its own fill before its first MFMA, and the two halo rows are fetched again by the
+// tile below.  Here
+//  - one workgroup owns ALL input channels, all nine taps and a group of up to CW_NA_MAX = 5 co tiles (80 channels): wave w
+//    owns the 16-channel ci group w (CIG = cin_s / 16 waves) and accumulates NA x 9 tiles (NA = co tiles / co groups, rounded up); a dy fragment feeds nine taps,
+//    an x fragment NA co tiles.  c_out > 80 adds co groups to the grid (their workgroups sit on one XCD and share x in L2).
+//  - a workgroup walks a CONTIGUOUS range of the 4 x 32 tiles in (image, column, row) order, i.e. down 32-pixel-wide
+//    columns; the x rows live in a rolling ring of CW_RING = 10 row slots (image row iy of the column in slot (iy + 1) %
+//    10): a tile reads six rows, of which the upper two are the previous tile's lower two and are NOT fetched again, while
+//    the four new rows of the next tile land in the four slots nobody reads.  The ring restarts (six rows, no overlap)
+//    at the first tile of a range and at the top of every column.  (Ranges of tiles instead of whole columns as the split
+//    unit: 32 x 10 columns at 320^2 over 256 CUs would run in two rounds; a restart costs one fill per range / column.)
+//  - staging overlaps the MFMAs: after the barrier that hands tile t to the readers, the pieces of tile t + 1 (next dy
+//    buffer of two, the four free ring slots) are issued and stay in flight while tile t multiplies; the wait for them
+//    is the vmcnt(0) in front of the next barrier (one stage in flight, as in the cooperative kernel).
+// LDS: x ring [plane = 64-channel block][slot][40 px][128 B] (row layout and swizzle of the tile kernel, read with
+// tr_frag_at), dy [buffer][co tile][tile row][32 positions x 32 B]: one 1-KiB DMA piece per (co tile, tile row); pixel p of
+// the row sits at position (p & 3) | ((p >> 3) & 3) << 2 | ((p >> 2) & 1) << 4, so that the four 16-lane groups of a
+// transposing read (pixels 8 g + k, then 8 g + 4 + k) read 512 consecutive bytes: no bank conflicts.
+constexpr int CW_RING = 10, CW_NA_MAX = 5;
+constexpr int CW_ROW_BYTES = TL_XP * 128;                      // one ring row of one plane: 5120
+constexpr int CW_PLANE_BYTES = CW_RING * CW_ROW_BYTES;         // 51200
+constexpr int CW_DYBUF_BYTES = CW_NA_MAX * TL_H * 1024;        // 20480
+constexpr int cw_lds_bytes(int cig) { return (cig / 4) * CW_PLANE_BYTES + 2 * CW_DYBUF_BYTES; }   // 140 KiB at 128 channels
+
+// Register budget: 8 waves = 2 per SIMD = 256 registers per lane.  The <T, 5, 8> instance holds 180 accumulator, 4 bias and
+// 20 + 8 fragment registers and compiles to 250-256 VGPRs without a spill to scratch (checked in the gfx950 ISA:
+// .vgpr_spill_count 0, no scratch_ instruction, in all 20 instances; a few SGPRs spill to VGPR lanes): there is no room
+// for another live value in the tile loop.  With 4 waves (cin_s 64) the accumulators go to AGPRs (up to 412 registers).
+template <typename T, int NA, int CIG>
+__global__ __launch_bounds__(64 * CIG, 1) void conv_wgrad_col3x3_kernel(WgradArgs p) {
+  constexpr int NW = CIG, PLANES = CIG / 4;
+  constexpr int DYK = (NA * TL_H + NW - 1) / NW;     // dy pieces per wave and tile
+  constexpr int NB = (NA + NW - 1) / NW;             // bias columns per wave
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+  unsigned char* dyb = smem + PLANES * CW_PLANE_BYTES;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int item = (blockIdx.x & 7) * p.per_xcd + (blockIdx.x >> 3);
+  if ((int)(blockIdx.x >> 3) >= p.per_xcd || item >= p.co_pairs * p.splits) return;
+  const int cg = item % p.co_pairs;                  // co group (co_pairs = number of co groups)
+  const int split = item / p.co_pairs;
+  const int cot_n = (p.cout_s + 15) >> 4;            // 16-row co tiles that exist
+  // first co tile of the group; the last group of a ragged c_out (9 tiles = 5 + 4) moves up to end at the last tile that
+  // exists instead of multiplying a tile of padding.  Its first `dup` tiles belong to the group before it: they are
+  // multiplied (a guard between the MFMAs would put branches into every shape's tile loop) but not stored.
+  const int ct0 = cg * NA + NA > cot_n ? cot_n - NA : cg * NA;
+  const int dup = cg * NA - ct0;
+
+  const int tw = p.w_out / TL_W, th = p.h_out / TL_H;
+  const long ntiles = (long)p.n * th * tw;
+  const int t_begin = (int)(ntiles * split / p.splits), t_end = (int)(ntiles * (split + 1) / p.splits);
+
+  const unsigned cin_b = (unsigned)p.cin_s * 2u, cout_b = (unsigned)p.cout_s * 2u;
+  const wg_rsrc_t rs_x = wg_make_rsrc(p.x, p.x_bytes);
+  const wg_rsrc_t rs_dy = wg_make_rsrc(p.dy, p.dy_bytes);
+  // x staging: lane = (pixel prow of an 8-pixel piece, 16-byte slot); wave w stages ring row 2 + w / PLANES of plane
+  // w % PLANES (five pieces); at a restart waves 0 .. 2 PLANES - 1 also stage rows 0 / 1
+  const int prow = lane >> 3, qs = (lane & 7) ^ swz(prow);
+  const int s_plane = wave % PLANES, s_row = wave / PLANES;
+  const unsigned x_c = (unsigned)(s_plane * 64 + qs * 8) * 2u;
+  // dy staging: lane = (position, 16-byte half of the co tile's 32 B)
+  const int dpos = lane >> 1;
+  const int dpx = (dpos & 3) | (((dpos >> 4) & 1) << 2) | (((dpos >> 2) & 3) << 3);
+  const int dch = (lane & 1) * 8;
+
+  // tile t = ((img * tw + col) * th + row): stage its dy into buffer `b` and its x rows j0 .. 5 (row j = image row
+  // 4 row - 1 + j) into ring slots (base + j) % CW_RING
+  auto stage = [&](int t, int b, int base, bool restart) {
+    const int tr = t % th, r0 = t / th;
+    const int tc = r0 % tw, img = r0 / tw;
+    const int ty0 = tr * TL_H, tx0 = tc * TL_W;
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+      // rr = 0: the wave's new row (j = 2 + s_row); rr = 1: restart rows (j = s_row < 2)
+      if (rr == 1 && !(restart && s_row < 2)) continue;
+      const int j = rr == 0 ? 2 + s_row : s_row;
+      int slot = base + j;
+      slot = slot >= CW_RING ? slot - CW_RING : slot;
+      const int iy = ty0 - 1 + j;
+      const unsigned row_off = (unsigned)((img * p.h_in + iy) * p.w_in) * cin_b + x_c;
+      unsigned char* dst = smem + s_plane * CW_PLANE_BYTES + slot * CW_ROW_BYTES;
+#pragma unroll
+      for (int i5 = 0; i5 < 5; ++i5) {
+        const int ix = tx0 - 4 + 8 * i5 + prow;
+        const bool ok = ((unsigned)iy < (unsigned)p.h_in) & ((unsigned)ix < (unsigned)p.w_in);
+        wg_dma16(rs_x, dst + i5 * 1024, ok ? row_off + (unsigned)ix * cin_b : 0xffffffffu);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < DYK; ++k) {
+      const int pid = wave + NW * k, a = pid >> 2, ty = pid & 3;
+      if (a < NA) {
+        const int co = (ct0 + a) * 16 + dch;
+        const unsigned off = (unsigned)((img * p.h_out + ty0 + ty) * p.w_out + tx0 + dpx) * cout_b + (unsigned)co * 2u;
+        wg_dma16(rs_dy, dyb + b * CW_DYBUF_BYTES + pid * 1024, co < p.cout_s ? off : 0xffffffffu);
+      }
+    }
+  };
+
+  // fragment addresses (lane constants): dy position 4 g + k (+ 16), x rows 3 + kx + 8 g + k (+ 4) of a ring row
+  const int fi = lane & 15, fg = lane >> 4, fk = fi >> 2;
+  const int dy_lo = (4 * fg + fk) * 32 + (fi & 3) * 8;
+  const int c_plane = (wave >> 2) % PLANES, c_grp = wave & 3;
+  const unsigned char* xpl = smem + c_plane * CW_PLANE_BYTES;
+
+  f32x4 acc[NA][9];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[a][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  // the bias gradient as the constant-one column: wave w sums co tiles w, w + NW, ... (one extra MFMA per tile row)
+  const bool do_bias = p.bpart != nullptr;
+  const bool bias_w = do_bias && wave < NA;      // wave-uniform
+  f32x4 accb[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) accb[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  bool staged = false;
+  int base = 0;                 // ring slot of row j = 0 of the tile being multiplied
+  for (int t = t_begin; t < t_end; ++t) {
+    const int buf = (t - t_begin) & 1;
+    if (!staged) {              // restart: everyone has finished reading the previous tile, then fill all six rows
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __syncthreads();
+      base = 0;
+      stage(t, buf, 0, true);
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // own pieces landed, own fragment reads of tile t - 1 done
+    __syncthreads();                                              // everyone's: tile t is readable, tile t - 1's slots are free
+    staged = false;
+    if (t + 1 < t_end && ((t + 1) % th) != 0) {
+      int nb = base + TL_H;
+      nb = nb >= CW_RING ? nb - CW_RING : nb;
+      stage(t + 1, buf ^ 1, nb, false);
+      staged = true;
+    }
+    int rowoff[TL_H + 2];
+#pragma unroll
+    for (int j = 0; j < TL_H + 2; ++j) {
+      int s = base + j;
+      s = s >= CW_RING ? s - CW_RING : s;
+      rowoff[j] = s * CW_ROW_BYTES;
+    }
+    const unsigned char* dcur = dyb + buf * CW_DYBUF_BYTES;
+#pragma unroll
+    for (int ty = 0; ty < TL_H; ++ty) {
+      u32x4 fa[NA];
+#pragma unroll
+      for (int a = 0; a < NA; ++a) {
+        const unsigned char* a0 = dcur + (a * TL_H + ty) * 1024 + dy_lo;
+        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
+        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 512));
+        fa[a][0] = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
+        fa[a][1] = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
+        fa[a][2] = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
+        fa[a][3] = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
+      }
+      if (bias_w) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+          u32x4 sel = fa[0];          // co tile wave + NW i (wave-uniform selects; a tile past NA is not stored)
+#pragma unroll
+          for (int aa = 1; aa < NA; ++aa) sel = (aa == wave + NW * i) ? fa[aa] : sel;
+          accb[i] = mfma16(as_vec8<T>(sel), as_vec8<T>(ones_frag<T>()), accb[i]);
+        }
+      }
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int ky = tap / 3, kx = tap - ky * 3;
+        const u32x4 fb = tr_frag_at(xpl + rowoff[ty + ky], 3 + kx, c_grp, lane);
+#pragma unroll
+        for (int a = 0; a < NA; ++a) acc[a][tap] = mfma16(as_vec8<T>(fa[a]), as_vec8<T>(fb), acc[a][tap]);
+      }
+    }
+    if (staged) {
+      base += TL_H;
+      base = base >= CW_RING ? base - CW_RING : base;
+    }
+  }
+
+  // bias row of this pixel split: column 0's lanes hold rows co + 4 g + r of co tile a
+  if (do_bias && (lane & 15) == 0) {
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int a = wave + NW * i, co = (ct0 + a) * 16 + 4 * fg;
+      if (a < NA && a >= dup && co < p.cout_s) *reinterpret_cast<f32x4*>(p.bpart + (size_t)split * p.cout_s + co) = accb[i];
+    }
+  }
+  // partial tiles to the workspace in the layout wgrad_reduce_kernel sums: [split][64 x 64 tile (tap, cib, cob)][a * 4 + b][lane];
+  // the last co group also zeroes the fragments of the co tiles that pad the last 64-channel block
+  const int tiles_n = 9 * p.ci_blocks * p.co_blocks;
+  f32x4* wsp = reinterpret_cast<f32x4*>(p.ws) + (size_t)split * tiles_n * 1024;
+  const int pad_to = (cg == p.co_pairs - 1) ? p.co_blocks * 4 : 0;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      if (a < dup) continue;
+      const int ct = ct0 + a;
+      const int tile = (tap * p.ci_blocks + c_plane) * p.co_blocks + (ct >> 2);
+      wsp[(size_t)tile * 1024 + ((ct & 3) * 4 + c_grp) * 64 + lane] = acc[a][tap];
+    }
+    for (int ct = cot_n; ct < pad_to; ++ct) {
+      const int tile = (tap * p.ci_blocks + c_plane) * p.co_blocks + (ct >> 2);
+      wsp[(size_t)tile * 1024 + ((ct & 3) * 4 + c_grp) * 64 + lane] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
   }
 }
 
@@ -886,7 +1098,9 @@ CGAN_KNOB(unsigned long long*, g_wgrad_ts, nullptr);
 extern "C" void cgan_debug_set_wgrad_tsbuf(void* p) { g_wgrad_ts = (unsigned long long*)p; }
 extern "C" void cgan_debug_set_wgrad_bias_fused(int v) { g_wgrad_bias_fused = v; }
 extern "C" void cgan_debug_set_wgrad_ws_cost(int pct) { g_wgrad_ws_cost_pct = pct > 0 ? pct : 100; }
-extern "C" void cgan_debug_set_wgrad_tile3x3(int v) { g_wgrad_tile = v; }   // 0: never the spatially tiled 3 x 3 kernel, 2: wherever it applies
+// 0: never a spatially tiled 3 x 3 kernel, 1: automatic, 2: wherever one applies, 3: the column-walking kernel on every
+// shape that meets its preconditions, however small (tests)
+extern "C" void cgan_debug_set_wgrad_tile3x3(int v) { g_wgrad_tile = v; }
 extern "C" void cgan_debug_set_wgrad_slots(int v) { g_wgrad_slots = v > 0 ? v : 512; }   // resident workgroups the planner assumes
 extern "C" void cgan_debug_set_wgrad_coop_chunk(int v) { g_wgrad_coop_chunk = (v == 32 || v == 64) ? v : 0; }   // 0: automatic
 
@@ -908,6 +1122,7 @@ struct WgradPlan {
   int coop, co_pairs, n_pairs, chunk;   // chunk: pixels per stage of the cooperative kernel (64 / 32)
   int g;                                // wave grid of the cooperative kernel: 2 (128 x 128 tile) or 4 (256 x 256, 16 waves)
   int tile;                             // the spatially tiled 3 x 3 kernel (conv_wgrad_tile3x3_kernel)
+  int col, co_groups, na;               // the column-walking tiled kernel (conv_wgrad_col3x3_kernel): co groups of `na` 16-row tiles
   long tiles() const { return (long)tap_slots * ci_blocks * co_blocks; }
 };
 
@@ -933,10 +1148,36 @@ static WgradPlan wgrad_plan(const CganConvDesc* d, bool have_ws = true) {
              (g_wgrad_dbg & 8) == 0 && (double)npix * cgan_cs(d->c_out) * 2.0 < 1.9e9 &&
              (npix >= (long)g_wgrad_coop_min_pix || pl.tiles() >= 256))
                 ? 1 : 0;
+  // Column-walking tiled kernel: 64 / 128 input channels.  Automatic for the SPADE gamma|beta gradients (128 hidden
+  // channels -> 2 C >= 40 channels), including the shapes with paired blocks that took the cooperative kernel.  The three
+  // other layers of the joint step that meet its preconditions keep the tile kernel below, as before: 64 -> 64 and
+  // 128 -> 32 at 64 x 160^2, 64 -> 32 at 32 x 160^2 (the new kernel forced on them: 233 -> 188, 245 -> 185, 90 -> 80 us,
+  // profiles/r07_wgrad_col3x3_ab.txt; moving them and deleting the tile kernel, which then only serves cin_s = 192,
+  // 256, ..., is a change of its own).
+  const bool tiled_shape = have_ws && !pl.fold && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->dilation == 1 &&
+                           d->pad_mode == CGAN_PAD_ZERO && !d->in_upsample && (d->w_out % TL_W) == 0 && (d->h_out % TL_H) == 0 &&
+                           (g_wgrad_dbg & (8 | 16)) == 0;
+  pl.col = (tiled_shape && (cin_s == 64 || cin_s == 128) &&
+            (g_wgrad_tile == 3 || (npix >= 65536 && (g_wgrad_tile == 2 || (g_wgrad_tile == 1 && cin_s == 128 && cgan_cs(d->c_out) >= 40)))))
+               ? 1 : 0;
+  pl.co_groups = pl.na = 0;
+  pl.tile = 0;
+  if (pl.col) {
+    pl.coop = 0;
+    pl.chunk = TL_W * TL_H;
+    const int cot = ceil_div(cgan_cs(d->c_out), 16);
+    pl.co_groups = ceil_div(cot, CW_NA_MAX);
+    pl.na = ceil_div(cot, pl.co_groups);
+    // one workgroup per CU (140 KiB of LDS): the tiles in (image, column, row) order are cut into `splits` equal ranges
+    const long ntiles = npix / (TL_W * TL_H);
+    long sp = g_wgrad_target < 0 ? -g_wgrad_target : (long)(g_wgrad_slots / 2) / pl.co_groups;
+    if (sp > ntiles) sp = ntiles;
+    pl.splits = sp < 1 ? 1 : (int)sp;
+    return pl;
+  }
   // spatially tiled 3 x 3 kernel: large maps of whole 4 x 32 pixel tiles, 64-channel input blocks, partial tiles through
-  // the workspace only; where the cooperative kernel cannot pair blocks (SPADE gamma|beta 128 -> 40 at 4 x 640^2: 438 ->
-  // 287 us, 128 -> 160 at 4 x 320^2: 292 -> 217 us; with paired blocks the cooperative kernel is as fast: 128 -> 80 548
-  // against 586 us).  Knob 2 forces it wherever it applies (tests).
+  // the workspace only; where the cooperative kernel cannot pair blocks and the column-walking kernel above is not taken
+  // (the layers named there).  Knob 2 forces a tiled kernel wherever one applies (tests).
   pl.tile = ((g_wgrad_tile == 2 || (g_wgrad_tile == 1 && !pl.coop)) && have_ws && !pl.fold && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 &&
              d->dilation == 1 && d->pad_mode == CGAN_PAD_ZERO && !d->in_upsample && (d->w_out % TL_W) == 0 &&
              (d->h_out % TL_H) == 0 && (cin_s % 64) == 0 && npix >= 65536 && (g_wgrad_dbg & (8 | 16)) == 0) ? 1 : 0;
@@ -1016,6 +1257,15 @@ static WgradPlan wgrad_plan(const CganConvDesc* d, bool have_ws = true) {
   return pl;
 }
 
+#ifdef CGAN_DEV
+// which kernel the plan takes for this call (with a workspace): 0 per-tap single-wave, 1 cooperative, 2 tile3x3, 3 col3x3
+extern "C" int cgan_debug_wgrad_plan_kind(const CganConvDesc* d) {
+  if (!d) return -1;
+  const WgradPlan pl = wgrad_plan(d);
+  return pl.col ? 3 : (pl.tile ? 2 : (pl.coop ? 1 : 0));
+}
+#endif
+
 extern "C" size_t cgan_conv2d_bwd_weight_workspace_bytes(const CganConvDesc* d) {
   if (!d || d->n <= 0 || d->h_out <= 0 || d->w_out <= 0 || d->c_in <= 0 || d->c_out <= 0 || d->kh <= 0 || d->kw <= 0)
     return 0;
@@ -1058,8 +1308,10 @@ extern "C" int cgan_conv2d_nhwc_bwd_weight(const void* x, const void* dy, float*
   a.coop = pl.coop; a.co_pairs = pl.co_pairs; a.n_pairs = pl.n_pairs;
   const int taps = d->kh * d->kw;
   CGAN_DEV_ONLY(a.dbg = g_wgrad_dbg; a.ts = g_wgrad_ts;)
-  const long items = (long)a.splits * (pl.tile ? (long)pl.co_blocks * pl.ci_blocks
-                                              : (pl.coop ? (long)pl.co_pairs * pl.n_pairs : pl.tiles()));
+  if (pl.col) a.co_pairs = pl.co_groups;
+  const long items = (long)a.splits * (pl.col ? (long)pl.co_groups
+                                              : pl.tile ? (long)pl.co_blocks * pl.ci_blocks
+                                                        : (pl.coop ? (long)pl.co_pairs * pl.n_pairs : pl.tiles()));
   a.per_xcd = (int)((items + 7) / 8);
   CGAN_REQUIRE(items < (1L << 30), "conv2d_nhwc_bwd_weight: grid too large");
   const unsigned gx = (unsigned)a.per_xcd * 8;
@@ -1073,10 +1325,10 @@ extern "C" int cgan_conv2d_nhwc_bwd_weight(const void* x, const void* dy, float*
     // the bias gradient inside the weight-gradient kernel (a constant-one GEMM column in the workgroups of N tile 0): one
     // partial row per pixel split (x 4 waves in the single-wave-tile kernel), as long as the rows fit; otherwise, and
     // without a workspace, the separate channel-sum pass below
-    const int rows = a.splits * ((pl.tile || pl.coop) ? 1 : 4);
+    const int rows = a.splits * ((pl.col || pl.tile || pl.coop) ? 1 : 4);
     // (not in the two variants without registers to spare: the cooperative kernel's 32-pixel stages, the tiled kernel with
     // four co tiles)
-    const bool variant_ok = pl.tile ? (pl.co_blocks == 1 && ceil_div(cgan_cs(d->c_out), 16) < 4)
+    const bool variant_ok = pl.col ? true : pl.tile ? (pl.co_blocks == 1 && ceil_div(cgan_cs(d->c_out), 16) < 4)
                                     : (!pl.coop || (pl.chunk == 64 && pl.g == 2));
     if (dbias && rows <= BIAS_MAX_ROWS && variant_ok && g_wgrad_bias_fused && CGAN_WTS(a) == nullptr) {
       a.bpart = a.ws + (size_t)pl.tiles() * (size_t)pl.splits * 64 * 64;
@@ -1119,7 +1371,23 @@ extern "C" int cgan_conv2d_nhwc_bwd_weight(const void* x, const void* dy, float*
     else if (mode == 1) { if (uni) WGRAD_LAUNCH(TT, 1, true); else WGRAD_LAUNCH(TT, 1, false); } \
     else { if (uni) WGRAD_LAUNCH(TT, 0, true); else WGRAD_LAUNCH(TT, 0, false); }                \
   } while (0)
-  if (pl.tile) {
+  if (pl.col) {
+#define COL_LAUNCH(TT, NN, GG)                                                                                         \
+  do {                                                                                                                 \
+    CGAN_BIG_LDS((conv_wgrad_col3x3_kernel<TT, NN, GG>));                                                              \
+    hipLaunchKernelGGL((conv_wgrad_col3x3_kernel<TT, NN, GG>), dim3(gx), dim3(64 * GG), cw_lds_bytes(GG), s, a);       \
+  } while (0)
+#define COL_NA(TT, GG)                                                                                                 \
+  do {                                                                                                                 \
+    if (pl.na == 1) COL_LAUNCH(TT, 1, GG); else if (pl.na == 2) COL_LAUNCH(TT, 2, GG); else if (pl.na == 3) COL_LAUNCH(TT, 3, GG); \
+    else if (pl.na == 4) COL_LAUNCH(TT, 4, GG); else COL_LAUNCH(TT, 5, GG);                                            \
+  } while (0)
+#define COL_CIG(TT) do { if (a.cin_s == 128) COL_NA(TT, 8); else COL_NA(TT, 4); } while (0)
+    if (d->dtype == CGAN_F16) COL_CIG(F16); else COL_CIG(BF16);
+#undef COL_CIG
+#undef COL_NA
+#undef COL_LAUNCH
+  } else if (pl.tile) {
     const size_t smem3 = TL_XH_BYTES + TL_DY_BYTES;
     // a single co block of <= 48 channels: only the co tiles that exist (the 16-row tiles past cout_s would multiply zeros)
     const int na = pl.co_blocks == 1 ? ceil_div(a.cout_s, 16) : 4;

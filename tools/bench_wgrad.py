@@ -46,7 +46,7 @@ def main():
     ap.add_argument("--atomic", action="store_true")
     ap.add_argument("--coop-min", type=int, default=-1, help="cgan_debug_set_wgrad_coop_min_pixels")
     ap.add_argument("--only", default="", help="substring filter on the shape name")
-    ap.add_argument("--tile", type=int, default=-1, help="cgan_debug_set_wgrad_tile3x3 (0 never, 1 default, 2 wherever it applies)")
+    ap.add_argument("--tile", type=int, default=-1, help="cgan_debug_set_wgrad_tile3x3 (0 never, 1 default, 2 wherever it applies, 3 the column-walking kernel at any size)")
     ap.add_argument("--bias", action="store_true", help="with the bias gradient (rides in the weight-gradient kernels)")
     args = ap.parse_args()
     dt = torch.float16 if args.dtype == "fp16" else torch.bfloat16
