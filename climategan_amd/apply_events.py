@@ -12,7 +12,8 @@ only compressed bytes come back to the host.
 
 Differences: ``--upload`` (comet) is refused; an existing output directory without ``--overwrite`` is refused with a
 message instead of the reference's ``input()`` prompt, which nobody answers in a batch job; images are read, inferred and
-written batch by batch rather than all held in memory; ``--dtype`` selects the kernels' 16-bit type.
+written batch by batch rather than all held in memory; ``--dtype`` selects the kernels' 16-bit type; ``--png_level 2`` asks
+the device PNG encoder for smaller files (same pixels; neither is an option of the reference's script).
 """
 import argparse
 import shutil
@@ -82,8 +83,14 @@ DTYPES = ("bf16", "fp16")
 EVENT_ORDER = ("flood", "wildfire", "smog", "mask", "input")       # the order infer_all fills its dict in, then the input
 
 
+class _Args(argparse.Namespace):
+    """``png_level`` is 1 unless the command line gives it: an attribute with a class default, so that the namespace of a
+    run without it -- what ``main`` prints under "Using args" -- holds the entries it held before the option existed."""
+    png_level = 1
+
+
 def parse_args(argv=None):
-    """apply_events.py:4-148 (same names, short forms, defaults and help) + ``--dtype``."""
+    """apply_events.py:4-148 (same names, short forms, defaults and help) + ``--dtype`` and ``--png_level``."""
     argv = list(sys.argv[1:] if argv is None else argv)
     for a in argv:
         key = a.split("=", 1)[0]
@@ -125,7 +132,11 @@ def parse_args(argv=None):
                         help="Zip the output directory as '{outdir.parent}/{outdir.name}.zip'")
     parser.add_argument("--dtype", default=None, choices=DTYPES,
                         help="G.set_compute_dtype: the kernels' 16-bit type (default: the trainer's)")
-    args = parser.parse_args(argv)
+    parser.add_argument("--png_level", type=int, default=argparse.SUPPRESS, choices=(1, 2),
+                        help="Not an option of the reference's script: the device PNG encoder's level. 1: fixed-Huffman "
+                        "blocks; 2: per row the smallest of a fixed, dynamic or stored block (smaller files, same pixels). "
+                        "Defaults to 1")
+    args = parser.parse_args(argv, namespace=_Args())
     if args.batch_size < 1:
         parser.error("--batch_size must be positive")
     if args.zip_outdir and args.output_path is None:
@@ -351,7 +362,7 @@ def main(argv=None):
                 width = x.shape[-1]
                 for event, im_u8 in events_to_uint8(events, x, args.save_input).items():
                     png.write(im_u8, [outdir / event_file_name(Path(p).stem, event, width, keep_ratio, args.no_cloudy)
-                                      for p in paths])
+                                      for p in paths], level=args.png_level)
 
     if args.zip_outdir:
         print("\n\u2022 Zipping output directory... ", end="", flush=True)

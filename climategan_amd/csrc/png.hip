@@ -4,6 +4,8 @@
 // File layout:  signature | IHDR | one IDAT per row | one closing IDAT | IEND.  The IDAT payloads form one zlib stream:
 //   78 01 | per row: [fixed-Huffman block (BFINAL 0), empty stored block (pads to a byte: .. 00 00 FF FF)] | 03 00 (final
 //   empty fixed block) | Adler-32.
+// At level 2 a row's block is the smallest of three codings of the same tokens: fixed Huffman, dynamic Huffman (a code built
+// from the row's own histogram, png_huffman.h) or stored.
 // Every row therefore encodes independently of every other one and ends on a byte boundary (the way pigz joins the output of
 // its threads), and every row's chunk carries its own CRC-32.
 //
@@ -15,6 +17,9 @@
 // No atomics on global memory and fixed-order reductions: the bytes of an image do not depend on the batch it is in or on
 // the run.
 #include "cgan_common.h"
+#include "png_huffman.h"
+
+#include <vector>
 
 namespace {
 
@@ -39,6 +44,30 @@ __host__ __device__ inline uint32_t png_slot_bytes(uint32_t m) { return 16u + pn
 struct PngLds {
   uint32_t prev, j1, d, len, flags, scratch, total;
 };
+// What level 2 adds behind that (byte offsets from PngLds::total, 3488 bytes).  The sorted counts are dead once the lengths
+// exist and give their place to the header tokens; the sort's symbol order gives its place to the codes.
+constexpr uint32_t PNG_SYMS = 288;          // 286 literal / length symbols, padded
+constexpr uint32_t PNG_H_HIST = 0;                              // uint32 [288]  token counts per symbol
+constexpr uint32_t PNG_H_SORTED = PNG_H_HIST + 4u * PNG_SYMS;   // uint32 [288]  sorted counts; then uint16 header tokens
+constexpr uint32_t PNG_H_CODES = PNG_H_SORTED + 4u * PNG_SYMS;  // uint16 [288]  symbols in sorted order; then the codes
+constexpr uint32_t PNG_H_LENS = PNG_H_CODES + 2u * PNG_SYMS;    // uint8 [320]   code lengths, the distance code's behind
+constexpr uint32_t PNG_H_CL = PNG_H_LENS + 320u;                // the code-length code: PngClCode
+constexpr uint32_t PNG_H_BYTES = PNG_H_CL + 288u;
+struct PngClCode {
+  uint32_t counts[png_huff::NUM_CL], sorted[png_huff::NUM_CL];
+  uint16_t order[png_huff::NUM_CL], codes[png_huff::NUM_CL];
+  uint8_t lens[png_huff::NUM_CL + 1];
+  uint32_t nlit, ndist, ntok, hclen, header_bits;   // of the dynamic block's header, 3-bit block header not counted
+};
+static_assert(sizeof(PngClCode) <= PNG_H_BYTES - PNG_H_CL, "PngClCode outgrew its place");
+// the level-2 arrays by name, declared only inside the level-2 branches: level 1 has none of them
+#define PNG_HUFFMAN_LDS(base)                                                                      \
+  [[maybe_unused]] unsigned char* const hs = (base);                                                \
+  [[maybe_unused]] uint32_t* const hist = reinterpret_cast<uint32_t*>(hs + PNG_H_HIST);             \
+  [[maybe_unused]] uint16_t* const codes = reinterpret_cast<uint16_t*>(hs + PNG_H_CODES);           \
+  [[maybe_unused]] uint16_t* const hdr_tokens = reinterpret_cast<uint16_t*>(hs + PNG_H_SORTED);     \
+  [[maybe_unused]] uint8_t* const lens = hs + PNG_H_LENS;                                           \
+  [[maybe_unused]] PngClCode* const cl = reinterpret_cast<PngClCode*>(hs + PNG_H_CL)
 __host__ __device__ inline PngLds png_lds(uint32_t m) {
   PngLds o;
   const uint32_t rowb = png_round_up(m - 1u, 16u);
@@ -123,6 +152,29 @@ __device__ inline uint32_t match_token(uint32_t l, bool dist3, uint32_t& nbits) 
   nbits = hb + eb + 5u;
   return bit_rev(huff, hb) | (ev << hb) | (dist << (hb + eb));
 }
+// ---- level 2: the same tokens under another code ------------------------------------------------------------------------
+// length symbol 257..285 of l = length - 3, its extra bits and their value
+__device__ inline uint32_t length_symbol(uint32_t l, uint32_t& eb, uint32_t& ev) {
+  eb = 0, ev = 0;
+  if (l < 8u) return 257u + l;
+  if (l == 255u) return 285u;
+  eb = (31u - (uint32_t)__clz(l)) - 2u;
+  ev = l & ((1u << eb) - 1u);
+  return 261u + 4u * eb + ((l >> eb) & 3u);
+}
+__device__ inline uint32_t symbol_extra_bits(uint32_t s) { return (s < 265u || s == 285u) ? 0u : (s - 261u) >> 2; }
+__device__ inline uint32_t fixed_code_bits(uint32_t s) { return s < 144u ? 8u : (s < 256u ? 9u : (s < 280u ? 7u : 8u)); }
+// The distance code is declared complete and never built: lengths {1, 1} (c = 1) or {1, 0, 1} (c = 3), so distance 1 (code
+// 0) is the bit 0 and distance 3 (code 2) the bit 1.
+__device__ inline uint32_t dynamic_match_token(uint32_t l, bool dist3, const uint16_t* codes, const uint8_t* lens,
+                                               uint32_t& nbits) {
+  uint32_t eb, ev;
+  const uint32_t s = length_symbol(l, eb, ev);
+  const uint32_t hb = lens[s];
+  nbits = hb + eb + 1u;
+  return codes[s] | (ev << hb) | ((dist3 ? 1u : 0u) << (hb + eb));
+}
+
 __device__ inline void emit_bits(uint32_t* bb, uint32_t pos, uint32_t v, uint32_t nbits) {
   const uint32_t wi = pos >> 5, sh = pos & 31u;
   atomicOr(&bb[wi], v << sh);
@@ -158,7 +210,10 @@ __device__ inline uint32_t png_filter(int f, uint32_t x, uint32_t a, uint32_t b,
   }
 }
 
-// one workgroup per (row, image).  row_len = w * c bytes.
+// one workgroup per (row, image).  row_len = w * c bytes.  LEVEL 1: fixed-Huffman blocks; LEVEL 2: per row the smallest of
+// the fixed, dynamic and stored coding (first on ties), PNG_H_BYTES more LDS behind PngLds::total.
+enum : uint32_t { PNG_FIXED = 1, PNG_DYNAMIC = 2, PNG_STORED = 0 };         // = BTYPE
+template <int LEVEL>
 __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restrict__ in, int h, int row_len, int c,
                                                          uint32_t* __restrict__ row_size, uint32_t* __restrict__ row_s1,
                                                          uint32_t* __restrict__ row_s2, uint8_t* __restrict__ staging,
@@ -304,12 +359,94 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
     }
   }
 
+  // ---- level 2: the tokens' histogram, a code built from it, the sizes of the three codings, the choice ------------------
+  [[maybe_unused]] uint32_t mode = PNG_FIXED, n_mode = 0, dyn_bits = 0;
+  if constexpr (LEVEL == 2) {
+    PNG_HUFFMAN_LDS(smem + o.total);
+    uint32_t* sorted = reinterpret_cast<uint32_t*>(hs + PNG_H_SORTED);
+    uint16_t* order = codes;
+    for (uint32_t k = t; k < PNG_SYMS; k += PNG_T) hist[k] = 0;
+    for (uint32_t k = t; k < 320u; k += PNG_T) lens[k] = 0;
+    __syncthreads();
+    for (uint32_t i = lo; i < hi; ++i) {
+      const uint32_t f = flags[i];
+      if (!(f & 1u)) continue;
+      uint32_t eb, ev;
+      atomicAdd(&hist[(f & 2u) ? length_symbol(lenm3[i], eb, ev) : (uint32_t)d[i]], 1u);
+    }
+    if (t == 0) atomicAdd(&hist[256], 1u);                 // the end of block
+    __syncthreads();
+    // used symbols in ascending order of (count, symbol): every symbol counts the ones before it
+    uint32_t used = 0;
+    for (uint32_t s = t; s < (uint32_t)png_huff::NUM_LITLEN; s += PNG_T) {
+      const uint32_t cnt = hist[s];
+      uint32_t rank = 0;
+      used = 0;
+      for (uint32_t u = 0; u < (uint32_t)png_huff::NUM_LITLEN; ++u) {
+        const uint32_t cu = hist[u];
+        used += cu != 0u ? 1u : 0u;
+        rank += (cu != 0u && (cu < cnt || (cu == cnt && u < s))) ? 1u : 0u;
+      }
+      if (cnt) {
+        sorted[rank] = cnt;
+        order[rank] = (uint16_t)s;
+      }
+    }
+    __syncthreads();
+    if (t == 0) {                                          // the serial part (png_huffman.h), one lane
+      png_huff::lengths_from_sorted(sorted, order, (int)used, png_huff::MAX_BITS, lens);
+      uint32_t nlit = png_huff::NUM_LITLEN;
+      while (nlit > 257u && lens[nlit - 1u] == 0) --nlit;
+      png_huff::codes_from_lengths(lens, (int)nlit, codes);
+      lens[nlit] = 1;                                      // the distance code's lengths follow in the header's sequence
+      lens[nlit + 1u] = c == 1 ? 1 : 0;
+      lens[nlit + 2u] = 1;
+      const uint32_t ndist = c == 1 ? 2u : 3u;
+      const uint32_t ntok = (uint32_t)png_huff::header_tokens(lens, (int)(nlit + ndist), hdr_tokens, cl->counts);
+      const int cl_used = png_huff::sort_counts(cl->counts, png_huff::NUM_CL, cl->sorted, cl->order);
+      for (int k = 0; k < png_huff::NUM_CL; ++k) cl->lens[k] = 0;
+      png_huff::lengths_from_sorted(cl->sorted, cl->order, cl_used, png_huff::CL_MAX_BITS, cl->lens);
+      png_huff::codes_from_lengths(cl->lens, png_huff::NUM_CL, cl->codes);
+      uint32_t hclen = png_huff::NUM_CL;
+      while (hclen > 4u && cl->lens[png_huff::cl_order((int)hclen - 1)] == 0) --hclen;
+      uint32_t hb = 5u + 5u + 4u + 3u * hclen;
+      for (uint32_t k = 0; k < (uint32_t)png_huff::NUM_CL; ++k) hb += cl->counts[k] * (cl->lens[k] + png_huff::cl_extra_bits(k));
+      cl->nlit = nlit, cl->ndist = ndist, cl->ntok = ntok, cl->hclen = hclen, cl->header_bits = hb;
+    }
+    __syncthreads();
+    uint32_t fb = 0, db = 0;                               // bits of all tokens and the end of block under either code
+    for (uint32_t s = t; s < (uint32_t)png_huff::NUM_LITLEN; s += PNG_T) {
+      const uint32_t cnt = hist[s], x = symbol_extra_bits(s);
+      fb += cnt * (fixed_code_bits(s) + x + (s > 256u ? 5u : 0u));
+      db += cnt * (lens[s] + x + (s > 256u ? 1u : 0u));
+    }
+    fb = block_sum(scratch, fb);
+    db = block_sum(scratch, db);
+    // block header | tokens, end of block | stored block: 3 bits, padding, 00 00 FF FF
+    const uint32_t n_fixed = (3u + fb + 3u + 7u) / 8u + 4u;
+    const uint32_t n_dynamic = (3u + cl->header_bits + db + 3u + 7u) / 8u + 4u;
+    const uint32_t n_stored = 1u + 4u + m + 1u + 4u;       // header and padding, LEN / NLEN, the bytes, the empty block
+    n_mode = n_fixed;
+    if (n_dynamic < n_mode) mode = PNG_DYNAMIC, n_mode = n_dynamic;
+    if (n_stored < n_mode) mode = PNG_STORED, n_mode = n_stored;
+    dyn_bits = db;
+  }
+
   // ---- bit offsets of the tokens: sum per piece, exclusive scan over the pieces ------------------------------------------
   uint32_t bits = 0;
   for (uint32_t i = lo; i < hi; ++i) {
     const uint32_t f = flags[i];
     if (!(f & 1u)) continue;
     uint32_t nb;
+    if constexpr (LEVEL == 2) {
+      PNG_HUFFMAN_LDS(smem + o.total);
+      if (mode == PNG_DYNAMIC) {
+        if (f & 2u) dynamic_match_token(lenm3[i], (f & 4u) != 0, codes, lens, nb);
+        else nb = lens[d[i]];
+        bits += nb;
+        continue;
+      }
+    }
     if (f & 2u) match_token(lenm3[i], (f & 4u) != 0, nb);
     else literal_token(d[i], nb);
     bits += nb;
@@ -325,11 +462,44 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
   const uint32_t token_bits = scratch[PNG_T - 1];
   uint32_t pos = 3u + scratch[t] - bits;
   // block: BFINAL 0, BTYPE 01 | tokens | end of block (7 zero bits) | stored block: BFINAL 0, BTYPE 00, padding, 00 00 FF FF
-  const uint32_t n = (3u + token_bits + 7u + 3u + 7u) / 8u + 4u;       // bytes of this row's deflate data
+  uint32_t n = (3u + token_bits + 7u + 3u + 7u) / 8u + 4u;             // bytes of this row's deflate data
+  if constexpr (LEVEL == 2) {
+    PNG_HUFFMAN_LDS(smem + o.total);
+    n = n_mode;
+    if (mode == PNG_DYNAMIC) pos += cl->header_bits;
+  }
   const uint32_t bb_words = png_round_up(png_row_data_max(m) + 8u, 16u) / 4u;
   for (uint32_t k = t; k < bb_words; k += PNG_T) bb[k] = 0;            // j0 / j1 are dead: the bit buffer takes their place
   __syncthreads();
-  if (t == 0) {
+  if constexpr (LEVEL == 2) {
+    PNG_HUFFMAN_LDS(smem + o.total);
+    if (mode == PNG_STORED) {                // 00 | LEN, NLEN | the filtered bytes | 00 | 00 00 FF FF, all with byte stores
+      uint8_t* b8 = reinterpret_cast<uint8_t*>(bb);
+      for (uint32_t k = t; k < m; k += PNG_T) b8[5u + k] = d[k];
+      if (t == 0) {
+        b8[1] = (uint8_t)m, b8[2] = (uint8_t)(m >> 8);
+        b8[3] = (uint8_t)~m, b8[4] = (uint8_t)(~m >> 8);
+        b8[n - 2u] = 0xFF, b8[n - 1u] = 0xFF;
+      }
+    } else if (t == 0) {
+      emit_bits(bb, 0, mode << 1, 3);
+      emit_bits(bb, (n - 2u) * 8u, 0xFFFFu, 16);
+      if (mode == PNG_DYNAMIC) {             // HLIT, HDIST, HCLEN | the code-length code | the run-length coded lengths
+        uint32_t p = 3u;
+        emit_bits(bb, p, cl->nlit - 257u, 5), p += 5u;
+        emit_bits(bb, p, cl->ndist - 1u, 5), p += 5u;
+        emit_bits(bb, p, cl->hclen - 4u, 4), p += 4u;
+        for (uint32_t k = 0; k < cl->hclen; ++k, p += 3u) emit_bits(bb, p, cl->lens[png_huff::cl_order((int)k)], 3);
+        for (uint32_t k = 0; k < cl->ntok; ++k) {
+          const uint32_t sym = hdr_tokens[k] & 31u, extra = hdr_tokens[k] >> 5, hb = cl->lens[sym];
+          const uint32_t nb = hb + png_huff::cl_extra_bits(sym);
+          emit_bits(bb, p, cl->codes[sym] | (extra << hb), nb);
+          p += nb;
+        }
+        emit_bits(bb, p + dyn_bits - lens[256], codes[256], lens[256]);      // the end of block, behind the tokens
+      }
+    }
+  } else if (t == 0) {
     emit_bits(bb, 0, 2u, 3);
     emit_bits(bb, (n - 2u) * 8u, 0xFFFFu, 16);
   }
@@ -337,6 +507,17 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
     const uint32_t f = flags[i];
     if (!(f & 1u)) continue;
     uint32_t nb;
+    if constexpr (LEVEL == 2) {
+      PNG_HUFFMAN_LDS(smem + o.total);
+      if (mode == PNG_STORED) break;
+      if (mode == PNG_DYNAMIC) {
+        const uint32_t v = (f & 2u) ? dynamic_match_token(lenm3[i], (f & 4u) != 0, codes, lens, nb) : (uint32_t)codes[d[i]];
+        if (!(f & 2u)) nb = lens[d[i]];
+        emit_bits(bb, pos, v, nb);
+        pos += nb;
+        continue;
+      }
+    }
     const uint32_t v = (f & 2u) ? match_token(lenm3[i], (f & 4u) != 0, nb) : literal_token(d[i], nb);
     emit_bits(bb, pos, v, nb);
     pos += nb;
@@ -502,9 +683,30 @@ extern "C" size_t cgan_png_workspace_bytes(int32_t n, int32_t h, int32_t w, int3
   return 4 * png_table_bytes(rows) + (size_t)rows * png_slot_bytes((uint32_t)w * c + 1u);
 }
 
-extern "C" int cgan_png_encode_u8(const uint8_t* in, int32_t n, int32_t h, int32_t w, int32_t c, uint8_t* out,
-                                  size_t out_pitch, int64_t* sizes, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int cgan_png_huffman_lengths(const uint32_t* counts, int32_t n, int32_t limit, uint8_t* lengths) {
+  CGAN_REQUIRE(counts && lengths, "cgan_png_huffman_lengths: null pointer");
+  CGAN_REQUIRE(n >= 1 && n <= 65535 && limit >= 1 && limit <= png_huff::MAX_BITS,
+               "cgan_png_huffman_lengths: n = %d, limit = %d: 1 <= n <= 65535 and 1 <= limit <= %d expected", n, limit,
+               png_huff::MAX_BITS);
+  std::vector<uint32_t> sorted((size_t)n);
+  std::vector<uint16_t> order((size_t)n);
+  const int used = png_huff::sort_counts(counts, n, sorted.data(), order.data());
+  CGAN_REQUIRE((int64_t)used <= (int64_t)1 << limit, "cgan_png_huffman_lengths: %d used symbols do not fit codes of %d bits",
+               used, limit);
+  uint64_t sum = 0;
+  for (int k = 0; k < used; ++k) sum += sorted[(size_t)k];
+  CGAN_REQUIRE(sum <= 0xffffffffull, "cgan_png_huffman_lengths: the counts sum to %llu, above 2^32 - 1",
+               (unsigned long long)sum);
+  for (int32_t s = 0; s < n; ++s) lengths[s] = 0;
+  png_huff::lengths_from_sorted(sorted.data(), order.data(), used, limit, lengths);
+  return CGAN_OK;
+}
+
+extern "C" int cgan_png_encode_u8_level(const uint8_t* in, int32_t n, int32_t h, int32_t w, int32_t c, int32_t level,
+                                        uint8_t* out, size_t out_pitch, int64_t* sizes, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
   CGAN_REQUIRE(in && out && sizes && workspace, "cgan_png_encode_u8: null pointer");
+  CGAN_REQUIRE(level == 1 || level == 2, "cgan_png_encode_u8: level = %d: 1 (fixed Huffman) or 2 (per-row choice) only", level);
   if (!png_shape_ok("cgan_png_encode_u8", n, h, w, c)) return CGAN_ERR_BAD_ARG;
   CGAN_REQUIRE(out_pitch >= cgan_png_bound_bytes(h, w, c), "cgan_png_encode_u8: out_pitch %zu is below the bound %zu",
                out_pitch, cgan_png_bound_bytes(h, w, c));
@@ -523,19 +725,20 @@ extern "C" int cgan_png_encode_u8(const uint8_t* in, int32_t n, int32_t h, int32
   uint8_t* staging = ws + 4 * tb;
   const uint32_t slot = png_slot_bytes(m);
   const PngLds lds = png_lds(m);
-  static bool attr_set = false;
-  if (!attr_set) {                           // the widest rows need more than the 64 KiB a launch gets by default
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&png_rows_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  auto* rows = level == 2 ? &png_rows_kernel<2> : &png_rows_kernel<1>;
+  const uint32_t lds_bytes = lds.total + (level == 2 ? PNG_H_BYTES : 0u);
+  static bool attr_set[2] = {false, false};
+  if (!attr_set[level - 1]) {                // the widest rows need more than the 64 KiB a launch gets by default
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rows), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024);
     if (e != hipSuccess) {
       cgan_set_error("cgan_png_encode_u8: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
       return CGAN_ERR_HIP;
     }
-    attr_set = true;
+    attr_set[level - 1] = true;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(png_rows_kernel, dim3(h, n), dim3(PNG_T), lds.total, s, in, h, w * c, c, row_size, row_s1, row_s2,
-                     staging, slot);
+  hipLaunchKernelGGL(rows, dim3(h, n), dim3(PNG_T), lds_bytes, s, in, h, w * c, c, row_size, row_s1, row_s2, staging, slot);
   CGAN_CHECK_LAUNCH("cgan_png_encode_u8 (rows)");
   hipLaunchKernelGGL(png_finish_kernel, dim3(n), dim3(PNG_T), 0, s, h, w, c, row_size, row_s1, row_s2, row_off, out,
                      out_pitch, reinterpret_cast<long long*>(sizes));
@@ -543,4 +746,9 @@ extern "C" int cgan_png_encode_u8(const uint8_t* in, int32_t n, int32_t h, int32
   hipLaunchKernelGGL(png_gather_kernel, dim3(h, n), dim3(PNG_T), 0, s, h, row_size, row_off, staging, slot, out, out_pitch);
   CGAN_CHECK_LAUNCH("cgan_png_encode_u8 (gather)");
   return CGAN_OK;
+}
+
+extern "C" int cgan_png_encode_u8(const uint8_t* in, int32_t n, int32_t h, int32_t w, int32_t c, uint8_t* out,
+                                  size_t out_pitch, int64_t* sizes, void* workspace, size_t workspace_bytes, void* stream) {
+  return cgan_png_encode_u8_level(in, n, h, w, c, 1, out, out_pitch, sizes, workspace, workspace_bytes, stream);
 }

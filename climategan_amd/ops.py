@@ -653,11 +653,14 @@ def png_bound_bytes(h: int, w: int, c: int) -> int:
     return bound
 
 
-def png_encode(img_u8: torch.Tensor):
+def png_encode(img_u8: torch.Tensor, level: int = 1):
     """uint8 [N, H, W, C] device tensor (contiguous, C = 1 grey or 3 RGB, W <= PNG_MAX_WIDTH) -> (buf uint8 [N, bound],
     sizes int64 [N]): ``buf[i, :sizes[i]]`` is the complete PNG file of image i.  Both stay on the device and
-    nothing is synchronised; everything else is refused here, before any launch."""
+    nothing is synchronised; everything else is refused here, before any launch.  ``level`` 1: fixed-Huffman blocks;
+    2: per row the smallest of a fixed, a dynamic and a stored block (smaller files, same pixels, same bound)."""
     _need_cuda(img_u8)
+    if level not in (1, 2):
+        raise RuntimeError("png_encode: level %r: 1 or 2 expected" % (level,))
     if img_u8.dtype != torch.uint8:
         raise RuntimeError("png_encode: uint8 input expected, got %s" % img_u8.dtype)
     if img_u8.dim() != 4 or img_u8.shape[3] not in (1, 3):
@@ -677,8 +680,8 @@ def png_encode(img_u8: torch.Tensor):
     ws = _empty(nbytes, dtype=torch.uint8, device=img_u8.device)
     buf = _empty((n, bound), dtype=torch.uint8, device=img_u8.device)
     sizes = _empty((n,), dtype=torch.int64, device=img_u8.device)
-    _lib.check(lib.cgan_png_encode_u8(_ptr(img_u8), n, h, w, c, _ptr(buf), bound, _ptr(sizes), _ptr(ws), nbytes, _stream()),
-               "cgan_png_encode_u8")
+    _lib.check(lib.cgan_png_encode_u8_level(_ptr(img_u8), n, h, w, c, int(level), _ptr(buf), bound, _ptr(sizes), _ptr(ws),
+                                            nbytes, _stream()), "cgan_png_encode_u8_level")
     return buf, sizes
 
 

@@ -20,9 +20,9 @@ def _pinned(nbytes):
     return _PINNED[:nbytes]
 
 
-def _fetch(img_u8):
+def _fetch(img_u8, level):
     """-> (host uint8 array [N, max length] in the pinned buffer, list of N lengths); valid until the next call."""
-    buf, sizes = ops.png_encode(img_u8)
+    buf, sizes = ops.png_encode(img_u8, level)
     lengths = sizes.cpu().tolist()
     n, longest = buf.shape[0], max(lengths)
     host = _pinned(n * longest).view(n, longest)
@@ -31,18 +31,19 @@ def _fetch(img_u8):
     return host.numpy(), lengths
 
 
-def encode(img_u8):
-    """uint8 [N, H, W, C] device tensor (C = 1 or 3) -> list of N ``bytes``, each a complete PNG file."""
-    host, lengths = _fetch(img_u8)
+def encode(img_u8, level=1):
+    """uint8 [N, H, W, C] device tensor (C = 1 or 3) -> list of N ``bytes``, each a complete PNG file.  ``level``: see
+    ``ops.png_encode``."""
+    host, lengths = _fetch(img_u8, level)
     return [host[i, :k].tobytes() for i, k in enumerate(lengths)]
 
 
-def write(img_u8, paths):
-    """Encode a batch on the device and write image i to ``paths[i]``."""
+def write(img_u8, paths, level=1):
+    """Encode a batch on the device (at ``level``, see ``ops.png_encode``) and write image i to ``paths[i]``."""
     paths = list(paths)
     if len(paths) != img_u8.shape[0]:
         raise ValueError("png.write: %d images but %d paths" % (img_u8.shape[0], len(paths)))
-    host, lengths = _fetch(img_u8)
+    host, lengths = _fetch(img_u8, level)
     for i, (path, k) in enumerate(zip(paths, lengths)):
         with open(path, "wb") as f:
             f.write(memoryview(host[i, :k]))

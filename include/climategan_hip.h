@@ -642,11 +642,22 @@ int cgan_binarize(const void* x, int32_t is_half, void* y, uint8_t* y_u8, float 
  *   65 + h * (12 + ceil((9 * (w * c + 1) + 13) / 8) + 4) bytes,
  * out_pitch must be at least that; the workspace (16-byte aligned) holds one staging slot per row.  The bytes of a file
  * depend on its image alone: not on the batch, not on the run.  The two size queries return 0 (and set the error text) for
- * a shape the encoder refuses. */
+ * a shape the encoder refuses.
+ * cgan_png_encode_u8_level: level 1 is the above, byte for byte (cgan_png_encode_u8 forwards with it).  Level 2 codes every
+ * row's tokens (same filter, same parse) three ways -- the fixed Huffman code, a dynamic Huffman block whose code is built
+ * from the row's own histogram, a stored block -- and keeps the smallest, the first on ties: no row's chunk is longer than
+ * at level 1, so the bound, the workspace and the pitch are the same.  Any other level: CGAN_ERR_BAD_ARG, nothing launched. */
 size_t cgan_png_bound_bytes(int32_t h, int32_t w, int32_t c);
 size_t cgan_png_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c);
 int cgan_png_encode_u8(const uint8_t* in, int32_t n, int32_t h, int32_t w, int32_t c, uint8_t* out, size_t out_pitch,
                        int64_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+int cgan_png_encode_u8_level(const uint8_t* in, int32_t n, int32_t h, int32_t w, int32_t c, int32_t level, uint8_t* out,
+                             size_t out_pitch, int64_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+/* The code construction of level 2's dynamic blocks, on the host (launches nothing): counts[n] -> lengths[n], a complete
+ * prefix code (Kraft sum exactly 1) of at most `limit` <= 15 bits over the symbols with a non-zero count, 0 for the others;
+ * the Huffman lengths where those stay within the limit; equal counts are ordered by symbol index.  One used symbol gets
+ * length 1.  More used symbols than 2^limit, or counts that sum above 2^32 - 1: CGAN_ERR_BAD_ARG. */
+int cgan_png_huffman_lengths(const uint32_t* counts, int32_t n, int32_t limit, uint8_t* lengths);
 
 /* Smog event (Trainer.compute_smog, climategan/trainer.py:1879-1939, parameters shared/trainer/events.yaml:9-14):
  * irradiance = srgb2lrgb(normalize(x)) (tutils.py:534-538), depth = normalize(1 / normalize(d, 0.3, 1), 0.1, 1)

@@ -1,5 +1,6 @@
-"""Time the "write" stage of apply_events for one batch of 16 outputs of 640 x 640 x 3: ``png.write`` (device encoder) against
-``PIL.Image.save`` from a 16-thread pool at PIL's default level and at ``compress_level=1``.
+"""Time the "write" stage of apply_events for one batch of 16 outputs of 640 x 640 x 3: ``png.write`` (device encoder) at
+level 1 (``gpu``) and at level 2 (``gpu_level2``: per-row dynamic Huffman / stored blocks) against ``PIL.Image.save`` from a
+16-thread pool at PIL's default level and at ``compress_level=1``.
 
 usage: python tools/time_png_write.py [--out DIR] [--reps 9] [--warmup 2] [--json FILE]
 
@@ -7,8 +8,8 @@ The images are real outputs: the small checkpoint's (tests/golden/ckpt_small opt
 weights) ``infer_all`` floods of generated photos -- noise alone would be unrepresentative.  Every repetition of every path
 starts from the same uint8 images where that path finds them (the device for ``png.write``, host arrays for PIL: the
 device-to-host copy of the raw pixels PIL needs is timed separately and reported, not added), writes 16 files and ends when
-the last file is closed; the three paths alternate inside each repetition and the medians are reported.  Prints seconds per
-image and bytes per image for all three, and one JSON line.
+the last file is closed; the four paths alternate inside each repetition and the medians are reported.  Prints seconds per
+image and bytes per image for all four, the size ratios level 2 / level 1 and level 2 / PIL default, and one JSON line.
 """
 import argparse
 import json
@@ -87,13 +88,14 @@ def main():
     tmp = tempfile.TemporaryDirectory() if args.out is None else None
     out = Path(tmp.name if tmp else args.out)
     out.mkdir(parents=True, exist_ok=True)
-    paths = {k: [out / ("%s_%02d.png" % (k, i)) for i in range(BATCH)] for k in ("gpu", "pil_default", "pil_level1")}
+    paths = {k: [out / ("%s_%02d.png" % (k, i)) for i in range(BATCH)] for k in ("gpu", "gpu_level2", "pil_default", "pil_level1")}
     pool = ThreadPoolExecutor(THREADS)
 
     def pil(kind, **kw):
         list(pool.map(lambda ip: Image.fromarray(ip[0]).save(ip[1], **kw), zip(host, paths[kind])))
 
     runs = {"gpu": lambda: png.write(dev, paths["gpu"]),
+            "gpu_level2": lambda: png.write(dev, paths["gpu_level2"], level=2),
             "pil_default": lambda: pil("pil_default"),
             "pil_level1": lambda: pil("pil_level1", compress_level=1)}
     times = {k: [] for k in runs}
@@ -108,6 +110,7 @@ def main():
             d2h.append(t)
     for i in range(BATCH):                                   # the device files hold the same pixels
         assert np.array_equal(np.asarray(Image.open(paths["gpu"][i])), host[i]), i
+        assert np.array_equal(np.asarray(Image.open(paths["gpu_level2"][i])), host[i]), i
     res = {"batch": BATCH, "shape": [SIZE, SIZE, 3], "reps": args.reps, "threads": THREADS,
            "raw_d2h_s_per_image": statistics.median(d2h) / BATCH}
     for k in runs:
@@ -117,6 +120,11 @@ def main():
         print("%-12s %.6f s/image (min %.6f, max %.6f)  %.0f bytes/image" % (
             k, res[k]["s_per_image"], *res[k]["s_per_image_min_max"], res[k]["bytes_per_image"]))
     res["size_ratio_gpu_over_pil_default"] = res["gpu"]["bytes_per_image"] / res["pil_default"]["bytes_per_image"]
+    res["size_ratio_level2_over_level1"] = res["gpu_level2"]["bytes_per_image"] / res["gpu"]["bytes_per_image"]
+    res["size_ratio_level2_over_pil_default"] = res["gpu_level2"]["bytes_per_image"] / res["pil_default"]["bytes_per_image"]
+    res["speedup_level2_over_level1"] = res["gpu"]["s_per_image"] / res["gpu_level2"]["s_per_image"]
+    print("size: level 2 / level 1 = %.4f, level 2 / PIL default = %.4f" % (
+        res["size_ratio_level2_over_level1"], res["size_ratio_level2_over_pil_default"]))
     res["speedup_gpu_over_pil_default"] = res["pil_default"]["s_per_image"] / res["gpu"]["s_per_image"]
     res["speedup_gpu_over_pil_level1"] = res["pil_level1"]["s_per_image"] / res["gpu"]["s_per_image"]
     line = json.dumps(res)
