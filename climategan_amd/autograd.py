@@ -595,46 +595,9 @@ def claim_relu_mask(out_t: torch.Tensor) -> bool:
     return True
 
 
-class BceLogitsFn(torch.autograd.Function):
-    """weight * sum BCEWithLogits(x, target) over the logical channels -> fp32 device scalar."""
-
-    @staticmethod
-    def forward(ctx, x_t, c, target, weight):
-        ctx.c = c
-        acc = torch.zeros(1, dtype=torch.float32, device=x_t.device)
-        dx = ops.bce_logits(ops.NHWC(x_t, c), target, weight * GRAD_SCALE, acc, want_grad=ctx.needs_input_grad[0])
-        ctx.save_for_backward(dx.t if dx is not None else None)
-        return acc[0] / GRAD_SCALE if GRAD_SCALE != 1.0 else acc[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dx_t,) = ctx.saved_tensors
-        if dx_t is None:
-            return None, None, None, None
-        return ops.scale_by_scalar(ops.NHWC(dx_t, ctx.c), g.reshape(1).float().contiguous()).t, None, None, None
-
-
-class MseConstFn(torch.autograd.Function):
-    """weight * sum (x - target)^2 over the logical channels (GANLoss with use_lsgan=True, losses.py:50-52)."""
-
-    @staticmethod
-    def forward(ctx, x_t, c, target, weight):
-        from . import _lib
-        ctx.c = c
-        acc = torch.zeros(1, dtype=torch.float32, device=x_t.device)
-        dx = torch.empty_like(x_t) if ctx.needs_input_grad[0] else None
-        _lib.check(_lib.load().cgan_mse_const_nhwc(ops._ptr(x_t), ops._DT[x_t.dtype], _npix(x_t), c, float(target),
-                                                   float(weight * GRAD_SCALE), ops._ptr(acc), ops._ptr(dx), ops._stream()),
-                   "cgan_mse_const_nhwc")
-        ctx.save_for_backward(dx)
-        return acc[0] / GRAD_SCALE if GRAD_SCALE != 1.0 else acc[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dx_t,) = ctx.saved_tensors
-        if dx_t is None:
-            return None, None, None, None
-        return ops.scale_by_scalar(ops.NHWC(dx_t, ctx.c), g.reshape(1).float().contiguous()).t, None, None, None
+def _scaled(dx, c, g):
+    """Backward of a scalar loss: the gradient its forward saved (None when the input wanted none) times the upstream scalar."""
+    return None if dx is None else ops.scale_by_scalar(ops.NHWC(dx, c), g.reshape(1).float().contiguous()).t
 
 
 class PainterAuxFn(torch.autograd.Function):
@@ -664,9 +627,7 @@ class PainterAuxFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_parts):
         (dfake,) = ctx.saved_tensors
-        if dfake is None:
-            return None, None, None, None, None, None
-        return ops.scale_by_scalar(ops.NHWC(dfake, 3), g.reshape(1).float().contiguous()).t, None, None, None, None, None
+        return _scaled(dfake, 3, g), None, None, None, None, None
 
 
 class ResizeBicubicFn(torch.autograd.Function):
@@ -687,45 +648,6 @@ class ResizeBicubicFn(torch.autograd.Function):
         _lib.check(_lib.load().cgan_resize_bicubic_bwd_nhwc(ops._ptr(dy), ops._ptr(dx), ops._DT[dy.dtype], dy.shape[0], c, h_in,
                                                             w_in, h_out, w_out, ops._stream()), "cgan_resize_bicubic_bwd_nhwc")
         return dx, None, None
-
-
-class HingeFn(torch.autograd.Function):
-    """weight * sum of HingeLoss.loss's per-element terms (reference losses.py:565-579) -> fp32 device scalar."""
-
-    @staticmethod
-    def forward(ctx, x_t, c, target_is_real, for_discriminator, weight):
-        ctx.c = c
-        acc = torch.zeros(1, dtype=torch.float32, device=x_t.device)
-        dx = ops.hinge_loss(ops.NHWC(x_t, c), target_is_real, for_discriminator, weight * GRAD_SCALE, acc,
-                            want_grad=ctx.needs_input_grad[0])
-        ctx.save_for_backward(dx.t if dx is not None else None)
-        return acc[0] / GRAD_SCALE if GRAD_SCALE != 1.0 else acc[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dx_t,) = ctx.saved_tensors
-        if dx_t is None:
-            return None, None, None, None, None
-        return ops.scale_by_scalar(ops.NHWC(dx_t, ctx.c), g.reshape(1).float().contiguous()).t, None, None, None, None
-
-
-class L1Fn(torch.autograd.Function):
-    """weight * sum |a - b| (b is a constant, as FeatMatchLoss detaches the real features, losses.py:99-101)."""
-
-    @staticmethod
-    def forward(ctx, a_t, b_t, c, weight):
-        ctx.c = c
-        acc = torch.zeros(1, dtype=torch.float32, device=a_t.device)
-        da = ops.l1_loss(ops.NHWC(a_t, c), ops.NHWC(b_t, c), weight * GRAD_SCALE, acc, want_grad=ctx.needs_input_grad[0])
-        ctx.save_for_backward(da.t if da is not None else None)
-        return acc[0] / GRAD_SCALE if GRAD_SCALE != 1.0 else acc[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (da_t,) = ctx.saved_tensors
-        if da_t is None:
-            return None, None, None, None
-        return ops.scale_by_scalar(ops.NHWC(da_t, ctx.c), g.reshape(1).float().contiguous()).t, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -869,33 +791,65 @@ class EntropyPairFromNchwFn(torch.autograd.Function):
 
 
 class _ScalarLossFn(torch.autograd.Function):
-    """Shared shape of the value+gradient loss kernels: ``run(acc, dx_or_None)`` fills the device scalar and, when the
-    input wants a gradient, the gradient of the accumulated term; backward scales it by the upstream scalar."""
+    """THE value+gradient loss Function: ``run(acc, want_grad)`` adds its weighted term into the fp32 device scalar ``acc``
+    and returns the gradient of that term w.r.t. the input map (an ops.NHWC; None unless ``want_grad``); backward scales it
+    by the upstream scalar.  The closures fold GRAD_SCALE into their weights; the returned value is unscaled."""
 
     @staticmethod
     def forward(ctx, x_t, c, run):
         acc = torch.zeros(1, dtype=torch.float32, device=x_t.device)
-        dx = torch.empty_like(x_t) if ctx.needs_input_grad[0] else None
-        run(acc, dx)                      # the closures fold GRAD_SCALE into their weights
+        dx = run(acc, ctx.needs_input_grad[0])
         ctx.c = c
-        ctx.save_for_backward(dx)
+        ctx.save_for_backward(dx.t if dx is not None else None)
         return acc[0] / GRAD_SCALE if GRAD_SCALE != 1.0 else acc[0]
 
     @staticmethod
     def backward(ctx, g):
         (dx,) = ctx.saved_tensors
-        if dx is None:
-            return None, None, None
-        return ops.scale_by_scalar(ops.NHWC(dx, ctx.c), g.reshape(1).float().contiguous()).t, None, None
+        return _scaled(dx, ctx.c, g), None, None
+
+
+def _kernel_loss(x: ops.NHWC, launch):
+    """_ScalarLossFn over a kernel called from here: ``launch(acc_ptr, dx_ptr)`` (dx_ptr null when no gradient is wanted)."""
+    def run(acc, want_grad):
+        dx = torch.empty_like(x.t) if want_grad else None
+        launch(ops._ptr(acc), ops._ptr(dx))
+        return ops.NHWC(dx, x.c) if want_grad else None
+    return _ScalarLossFn.apply(x.t, x.c, run)
+
+
+# the GAN-side terms, ``weight * sum(term)`` over the logical channels (the ops.* wrappers split maps of 2 GiB and more)
+def bce_logits_loss(pred: ops.NHWC, target: float, weight: float):
+    """weight * sum BCEWithLogits(pred, target) against a constant target."""
+    return _ScalarLossFn.apply(pred.t, pred.c, lambda acc, want_grad: ops.bce_logits(
+        pred, target, weight * GRAD_SCALE, acc, want_grad=want_grad))
+
+
+def mse_const_loss(pred: ops.NHWC, target: float, weight: float):
+    """weight * sum (pred - target)^2 (GANLoss with use_lsgan=True, losses.py:50-52)."""
+    return _ScalarLossFn.apply(pred.t, pred.c, lambda acc, want_grad: ops.mse_const(
+        pred, target, weight * GRAD_SCALE, acc, want_grad=want_grad))
+
+
+def hinge_loss(pred: ops.NHWC, target_is_real: bool, for_discriminator: bool, weight: float):
+    """weight * sum of HingeLoss.loss's per-element terms (reference losses.py:565-579)."""
+    return _ScalarLossFn.apply(pred.t, pred.c, lambda acc, want_grad: ops.hinge_loss(
+        pred, target_is_real, for_discriminator, weight * GRAD_SCALE, acc, want_grad=want_grad))
+
+
+def l1_loss(a: ops.NHWC, b: ops.NHWC, weight: float):
+    """weight * sum |a - b|; b is a constant (FeatMatchLoss detaches the real features, losses.py:99-101)."""
+    return _ScalarLossFn.apply(a.t, a.c, lambda acc, want_grad: ops.l1_loss(
+        a, b, weight * GRAD_SCALE, acc, want_grad=want_grad))
 
 
 def softmax_ce(logits: ops.NHWC, target: torch.Tensor):
     """nn.CrossEntropyLoss (mean over pixels); target int64 [n, h, w]."""
     n = _npix(logits.t)
     tgt = target.contiguous().long()
-    return _ScalarLossFn.apply(logits.t, logits.c, lambda acc, dx: _call(
-        "cgan_softmax_ce_nhwc", ops._ptr(logits.t), ops._ptr(tgt), logits.dtype_id, n, logits.c, GRAD_SCALE / n, ops._ptr(acc),
-        ops._ptr(dx), ops._stream()))
+    return _kernel_loss(logits, lambda acc, dx: _call(
+        "cgan_softmax_ce_nhwc", ops._ptr(logits.t), ops._ptr(tgt), logits.dtype_id, n, logits.c, GRAD_SCALE / n, acc, dx,
+        ops._stream()))
 
 
 def tv_loss(x: ops.NHWC, tvloss_weight=1.0):
@@ -903,26 +857,25 @@ def tv_loss(x: ops.NHWC, tvloss_weight=1.0):
     b, h, w, c = x.n, x.h, x.w, x.c
     wh = GRAD_SCALE * tvloss_weight * 2.0 / (c * (h - 1) * w) / b
     ww = GRAD_SCALE * tvloss_weight * 2.0 / (c * h * (w - 1)) / b
-    return _ScalarLossFn.apply(x.t, c, lambda acc, dx: _call(
-        "cgan_tv_nhwc", ops._ptr(x.t), x.dtype_id, b, h, w, c, wh, ww, ops._ptr(acc), ops._ptr(dx), ops._stream()))
+    return _kernel_loss(x, lambda acc, dx: _call(
+        "cgan_tv_nhwc", ops._ptr(x.t), x.dtype_id, b, h, w, c, wh, ww, acc, dx, ops._stream()))
 
 
 def minent_loss(p: ops.NHWC, version=1, lambda_var=0.1):
     """MinentLoss.__call__ (losses.py:185-196) on a probability map."""
     n = _npix(p.t)
     ws = torch.empty(4096, dtype=torch.float32, device=p.t.device)          # CGAN_MINENT_WORKSPACE_FLOATS
-    return _ScalarLossFn.apply(p.t, p.c, lambda acc, dx: _call(
-        "cgan_minent_nhwc", ops._ptr(p.t), p.dtype_id, n, p.c, int(version), float(lambda_var), GRAD_SCALE, ops._ptr(acc),
-        ops._ptr(dx), ops._ptr(ws), ops._stream()))
+    return _kernel_loss(p, lambda acc, dx: _call(
+        "cgan_minent_nhwc", ops._ptr(p.t), p.dtype_id, n, p.c, int(version), float(lambda_var), GRAD_SCALE, acc, dx,
+        ops._ptr(ws), ops._stream()))
 
 
 def bce_logits_map(x: ops.NHWC, target: torch.Tensor):
     """nn.BCEWithLogitsLoss(x, target) with a target map [n, 1, h, w] (fp32)."""
     n = _npix(x.t)
     tgt = target.contiguous().float()
-    return _ScalarLossFn.apply(x.t, x.c, lambda acc, dx: _call(
-        "cgan_bce_logits_map_nhwc", ops._ptr(x.t), ops._ptr(tgt), x.dtype_id, n, GRAD_SCALE / n, ops._ptr(acc), ops._ptr(dx),
-        ops._stream()))
+    return _kernel_loss(x, lambda acc, dx: _call(
+        "cgan_bce_logits_map_nhwc", ops._ptr(x.t), ops._ptr(tgt), x.dtype_id, n, GRAD_SCALE / n, acc, dx, ops._stream()))
 
 
 def ground_intersection(p: ops.NHWC, ground: torch.Tensor):
@@ -939,9 +892,8 @@ def advent_wgan(d_out: ops.NHWC, target: float):
     """-mean(y * D + (1 - y) * (1 - D)) (losses.py:498-499) for a scalar domain label y."""
     n = _npix(d_out.t) * d_out.c
     a, b = -GRAD_SCALE * (2.0 * target - 1.0) / n, -GRAD_SCALE * (1.0 - target) / n
-    return _ScalarLossFn.apply(d_out.t, d_out.c, lambda acc, dx: _call(
-        "cgan_affine_sum_nhwc", ops._ptr(d_out.t), d_out.dtype_id, _npix(d_out.t), d_out.c, a, b, ops._ptr(acc),
-        ops._ptr(dx), ops._stream()))
+    return _kernel_loss(d_out, lambda acc, dx: _call(
+        "cgan_affine_sum_nhwc", ops._ptr(d_out.t), d_out.dtype_id, _npix(d_out.t), d_out.c, a, b, acc, dx, ops._stream()))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1078,6 +1030,6 @@ def sigm_loss(pred: ops.NHWC, target: torch.Tensor, gmweight=0.5, scales=4):
     b, h, w = pred.n, pred.h, pred.w
     nbytes = lib.cgan_sigm_loss_workspace_bytes(b, h, w)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.t.device)
-    return _ScalarLossFn.apply(pred.t, pred.c, lambda acc, dx: _lib.check(lib.cgan_sigm_loss_nhwc(
-        ops._ptr(pred.t), ops._ptr(tgt), pred.dtype_id, b, h, w, float(gmweight), int(scales), GRAD_SCALE, ops._ptr(acc),
-        ops._ptr(dx), ops._ptr(ws), nbytes, ops._stream()), "cgan_sigm_loss_nhwc"))
+    return _kernel_loss(pred, lambda acc, dx: _lib.check(lib.cgan_sigm_loss_nhwc(
+        ops._ptr(pred.t), ops._ptr(tgt), pred.dtype_id, b, h, w, float(gmweight), int(scales), GRAD_SCALE, acc, dx,
+        ops._ptr(ws), nbytes, ops._stream()), "cgan_sigm_loss_nhwc"))

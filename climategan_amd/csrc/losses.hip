@@ -1,21 +1,135 @@
-// Masker-side losses (climategan/losses.py:106-196, 444-524) with their gradients, on the NHWC 16-bit maps the
-// decoders produce.  Every entry point ACCUMULATES `weight * sum(...)` into a device fp32 scalar and (optionally)
-// writes the gradient of that term.  HBM-bound elementwise / reduction work.
+// Every loss term with its gradient, on 16-bit NHWC maps: the GAN-side terms (climategan/losses.py:27-104, 550-593: BCE /
+// LSGAN / hinge against a constant target, L1 between two maps) and the Masker-side ones (losses.py:106-196, 444-524) with
+// the probability / entropy maps they consume.  Every loss entry point ACCUMULATES `weight * sum(...)` into a device fp32
+// scalar and (optionally) writes the gradient of that term.  HBM-bound elementwise / reduction work.
 #include "cgan_common.h"
+
+#define LOSS_LAUNCH(dtype, KERNEL, ...)                                     \
+  do {                                                                      \
+    if ((dtype) == CGAN_F16) hipLaunchKernelGGL(KERNEL<F16>, __VA_ARGS__);  \
+    else hipLaunchKernelGGL(KERNEL<BF16>, __VA_ARGS__);                     \
+  } while (0)
+#define LOSS_LAUNCH2(dtype, KERNEL, ARG, ...)                                     \
+  do {                                                                            \
+    if ((dtype) == CGAN_F16) hipLaunchKernelGGL((KERNEL<F16, ARG>), __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<BF16, ARG>), __VA_ARGS__);                    \
+  } while (0)
+#define LOSS_CHECK_DT(name) CGAN_REQUIRE(dtype == CGAN_F16 || dtype == CGAN_BF16, name ": bad dtype %d", dtype)
 
 namespace {
 
-inline int grid_ml(long total) {
+// blocks of 256 threads for `total` work items (the kernels stride over the rest), at most `cap`: 4096 for the Masker-side
+// kernels (minent leaves one partial per block: <= CGAN_MINENT_WORKSPACE_FLOATS); the GAN-side entry points pass their own
+inline int grid_of(long total, int cap = 4096) {
   long g = (total + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
+// block-level sum -> one atomic per block
 __device__ __forceinline__ void block_add(float v, float* dst) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   __shared__ float part[4];
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(dst, part[0] + part[1] + part[2] + part[3]);
+}
+
+// ---- one constant-target term per element of the c logical channels (pad channels: no term, gradient 0) -------------
+// A Term maps x to (l, g): loss += weight * sum l, dx = weight * g.
+// nn.BCEWithLogitsLoss: l = max(x,0) - x t + log1p(exp(-|x|)), g = sigmoid(x) - t
+struct BceTerm {
+  float target;
+  __device__ __forceinline__ void operator()(float x, float& l, float& g) const {
+    l = fmaxf(x, 0.f) - x * target + log1pf(__expf(-fabsf(x)));
+    g = 1.f / (1.f + __expf(-x)) - target;
+  }
+};
+// nn.MSELoss (GANLoss with use_lsgan=True, climategan/losses.py:50-52): l = (x - t)^2, g = 2 (x - t)
+struct MseTerm {
+  float target;
+  __device__ __forceinline__ void operator()(float x, float& l, float& g) const {
+    const float d = x - target;
+    l = d * d;
+    g = 2.f * d;
+  }
+};
+// HingeLoss (climategan/losses.py:550-593): discriminator side (hinged) l = max(0, 1 - sgn x)  [= -min(sgn x - 1, 0)],
+// g = -sgn where 1 - sgn x > 0 (half of it on an exact tie, torch.min's rule); generator side (not hinged) l = -sgn x, g = -sgn
+struct HingeTerm {
+  float sgn;
+  int hinged;
+  __device__ __forceinline__ void operator()(float x, float& l, float& g) const {
+    const float s = sgn;       // a local: with the member read inside the ternaries they compile to branches, not selects
+    const float mval = s * x - 1.f;                   // min(mval, 0) is what the reference averages
+    if (hinged) {
+      l = mval < 0.f ? -mval : 0.f;
+      g = mval < 0.f ? -s : (mval == 0.f ? -0.5f * s : 0.f);
+    } else {
+      l = -s * x;
+      g = -s;
+    }
+  }
+};
+template <typename T, typename Term>
+__global__ __launch_bounds__(256) void pointwise_loss_kernel(const uint16_t* __restrict__ x, Term term, float weight,
+                                                             float* __restrict__ loss, uint16_t* __restrict__ dx, int cs,
+                                                             int c, long groups) {
+  const int cg_total = cs / 8;
+  float acc = 0.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
+    const int cg = (int)(i % cg_total);
+    const u32x4 v = reinterpret_cast<const u32x4*>(x)[i];
+    u32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float a[2], gr[2];
+      unpack2<T>(v[e], a[0], a[1]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const bool live = cg * 8 + 2 * e + h < c;
+        float l, g;
+        term(a[h], l, g);
+        acc += live ? l : 0.f;
+        gr[h] = live ? weight * g : 0.f;
+      }
+      r[e] = pack2<T>(gr[0], gr[1]);
+    }
+    if (dx) reinterpret_cast<u32x4*>(dx)[i] = r;
+  }
+  block_add(acc * weight, loss);
+}
+template <typename Term>
+void launch_pointwise_loss(const void* x, int32_t dtype, int64_t npix, int32_t c, Term term, float weight, float* loss_accum,
+                           void* dx, void* stream) {
+  const int cs = cgan_cs(c);
+  const long groups = npix * (cs / 8);
+  LOSS_LAUNCH2(dtype, pointwise_loss_kernel, Term, dim3(grid_of(groups, 8192)), dim3(256), 0, (hipStream_t)stream,
+               (const uint16_t*)x, term, weight, loss_accum, (uint16_t*)dx, cs, c, groups);
+}
+
+// nn.L1Loss pieces: loss += weight * sum|a - b|;  da = weight * sign(a - b)
+template <typename T>
+__global__ __launch_bounds__(256) void l1_kernel(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b,
+                                                 float weight, float* __restrict__ loss, uint16_t* __restrict__ da,
+                                                 long groups) {
+  float acc = 0.f;
+#pragma unroll 2
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
+    const u32x4 va = CGAN_LD_STREAM(reinterpret_cast<const u32x4*>(a) + i);
+    const u32x4 vb = CGAN_LD_STREAM(reinterpret_cast<const u32x4*>(b) + i);
+    u32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float a0, a1, b0, b1;
+      unpack2<T>(va[e], a0, a1);
+      unpack2<T>(vb[e], b0, b1);
+      const float d0 = a0 - b0, d1 = a1 - b1;
+      acc += fabsf(d0) + fabsf(d1);
+      r[e] = pack2<T>(d0 > 0.f ? weight : (d0 < 0.f ? -weight : 0.f), d1 > 0.f ? weight : (d1 < 0.f ? -weight : 0.f));
+    }
+    if (da) CGAN_ST_STREAM(r, reinterpret_cast<u32x4*>(da) + i);
+  }
+  block_add(acc * weight, loss);
 }
 
 // ---- channel softmax (torch.softmax(s, dim=1)) and its backward; sigmoid pair [p, 1 - p] (trainer.py:1533-1534) ----
@@ -353,22 +467,53 @@ __global__ __launch_bounds__(256) void entropy_pair_nchw_bwd_kernel(const float*
 }
 }  // namespace
 
-#define ML_DISPATCH(dtype, KERNEL, ...)                                     \
-  do {                                                                      \
-    if ((dtype) == CGAN_F16) hipLaunchKernelGGL(KERNEL<F16>, __VA_ARGS__);  \
-    else hipLaunchKernelGGL(KERNEL<BF16>, __VA_ARGS__);                     \
-  } while (0)
-#define ML_DISPATCH2(dtype, KERNEL, FLAG, ...)                                  \
-  do {                                                                          \
-    if ((dtype) == CGAN_F16) hipLaunchKernelGGL((KERNEL<F16, FLAG>), __VA_ARGS__);  \
-    else hipLaunchKernelGGL((KERNEL<BF16, FLAG>), __VA_ARGS__);                 \
-  } while (0)
-#define ML_CHECK_DT(name) CGAN_REQUIRE(dtype == CGAN_F16 || dtype == CGAN_BF16, name ": bad dtype %d", dtype)
+extern "C" int cgan_bce_logits_nhwc(const void* x, int32_t dtype, int64_t npix, int32_t c, float target, float weight,
+                                    float* loss_accum, void* dx, void* stream) {
+  CGAN_REQUIRE(x && loss_accum, "bce_logits: null pointer");
+  LOSS_CHECK_DT("bce_logits");
+  CGAN_REQUIRE(npix > 0 && c > 0, "bce_logits: bad shape");
+  launch_pointwise_loss(x, dtype, npix, c, BceTerm{target}, weight, loss_accum, dx, stream);
+  CGAN_CHECK_LAUNCH("bce_logits");
+  return CGAN_OK;
+}
+extern "C" int cgan_mse_const_nhwc(const void* x, int32_t dtype, int64_t npix, int32_t c, float target, float weight,
+                                   float* loss_accum, void* dx, void* stream) {
+  CGAN_REQUIRE(x && loss_accum, "mse_const: null pointer");
+  LOSS_CHECK_DT("mse_const");
+  CGAN_REQUIRE(npix > 0 && c > 0, "mse_const: bad shape");
+  launch_pointwise_loss(x, dtype, npix, c, MseTerm{target}, weight, loss_accum, dx, stream);
+  CGAN_CHECK_LAUNCH("mse_const");
+  return CGAN_OK;
+}
+extern "C" int cgan_hinge_nhwc(const void* x, int32_t dtype, int64_t npix, int32_t c, int32_t target_is_real,
+                               int32_t for_discriminator, float weight, float* loss_accum, void* dx, void* stream) {
+  CGAN_REQUIRE(x && loss_accum, "hinge: null pointer");
+  LOSS_CHECK_DT("hinge");
+  CGAN_REQUIRE(npix > 0 && c > 0, "hinge: bad shape");
+  CGAN_REQUIRE(for_discriminator || target_is_real, "hinge: The generator's hinge loss must be aiming for real");
+  launch_pointwise_loss(x, dtype, npix, c, HingeTerm{target_is_real ? 1.f : -1.f, for_discriminator ? 1 : 0}, weight,
+                        loss_accum, dx, stream);
+  CGAN_CHECK_LAUNCH("hinge");
+  return CGAN_OK;
+}
+extern "C" int cgan_l1_nhwc(const void* a, const void* b, int32_t dtype, int64_t numel, float weight, float* loss_accum,
+                            void* da, void* stream) {
+  CGAN_REQUIRE(a && b && loss_accum, "l1: null pointer");
+  LOSS_CHECK_DT("l1");
+  CGAN_REQUIRE(numel > 0 && (numel % 8) == 0, "l1: numel must be a positive multiple of 8");
+  const long groups = numel / 8;
+  // at most 2048 blocks (one full round of the chip): every block ends in an atomic on the same address, and 8192 of them
+  // were most of this kernel's time on the large VGG / discriminator maps
+  LOSS_LAUNCH(dtype, l1_kernel, dim3(grid_of(groups, 2048)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)a,
+              (const uint16_t*)b, weight, loss_accum, (uint16_t*)da, groups);
+  CGAN_CHECK_LAUNCH("l1");
+  return CGAN_OK;
+}
 
 extern "C" int cgan_softmax_nhwc(const void* x, void* y, int32_t dtype, int64_t npix, int32_t c, void* stream) {
   CGAN_REQUIRE(x && y && npix > 0 && c > 0, "softmax: bad arguments");
-  ML_CHECK_DT("softmax");
-  ML_DISPATCH(dtype, softmax_fwd_kernel, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
+  LOSS_CHECK_DT("softmax");
+  LOSS_LAUNCH(dtype, softmax_fwd_kernel, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
               (uint16_t*)y, c, cgan_cs(c), (long)npix);
   CGAN_CHECK_LAUNCH("softmax");
   return CGAN_OK;
@@ -376,24 +521,24 @@ extern "C" int cgan_softmax_nhwc(const void* x, void* y, int32_t dtype, int64_t 
 extern "C" int cgan_softmax_bwd_nhwc(const void* y, const void* dy, void* dx, int32_t dtype, int64_t npix, int32_t c,
                                      void* stream) {
   CGAN_REQUIRE(y && dy && dx && npix > 0 && c > 0, "softmax_bwd: bad arguments");
-  ML_CHECK_DT("softmax_bwd");
-  ML_DISPATCH(dtype, softmax_bwd_kernel, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)y,
+  LOSS_CHECK_DT("softmax_bwd");
+  LOSS_LAUNCH(dtype, softmax_bwd_kernel, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)y,
               (const uint16_t*)dy, (uint16_t*)dx, c, cgan_cs(c), (long)npix);
   CGAN_CHECK_LAUNCH("softmax_bwd");
   return CGAN_OK;
 }
 extern "C" int cgan_sigmoid_pair_nhwc(const void* x, void* y, int32_t dtype, int64_t npix, void* stream) {
   CGAN_REQUIRE(x && y && npix > 0, "sigmoid_pair: bad arguments");
-  ML_CHECK_DT("sigmoid_pair");
-  ML_DISPATCH(dtype, sigmoid_pair_fwd_kernel, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
+  LOSS_CHECK_DT("sigmoid_pair");
+  LOSS_LAUNCH(dtype, sigmoid_pair_fwd_kernel, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
               (uint16_t*)y, (long)npix);
   CGAN_CHECK_LAUNCH("sigmoid_pair");
   return CGAN_OK;
 }
 extern "C" int cgan_sigmoid_pair_bwd_nhwc(const void* y, const void* dy, void* dx, int32_t dtype, int64_t npix, void* stream) {
   CGAN_REQUIRE(y && dy && dx && npix > 0, "sigmoid_pair_bwd: bad arguments");
-  ML_CHECK_DT("sigmoid_pair_bwd");
-  ML_DISPATCH(dtype, sigmoid_pair_bwd_kernel, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)y,
+  LOSS_CHECK_DT("sigmoid_pair_bwd");
+  LOSS_LAUNCH(dtype, sigmoid_pair_bwd_kernel, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)y,
               (const uint16_t*)dy, (uint16_t*)dx, (long)npix);
   CGAN_CHECK_LAUNCH("sigmoid_pair_bwd");
   return CGAN_OK;
@@ -401,8 +546,8 @@ extern "C" int cgan_sigmoid_pair_bwd_nhwc(const void* y, const void* dy, void* d
 extern "C" int cgan_softmax_ce_nhwc(const void* logits, const int64_t* target, int32_t dtype, int64_t npix, int32_t c,
                                     float weight, float* loss_accum, void* dlogits, void* stream) {
   CGAN_REQUIRE(logits && target && loss_accum && npix > 0 && c > 0, "softmax_ce: bad arguments");
-  ML_CHECK_DT("softmax_ce");
-  ML_DISPATCH(dtype, softmax_ce_kernel, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)logits,
+  LOSS_CHECK_DT("softmax_ce");
+  LOSS_LAUNCH(dtype, softmax_ce_kernel, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)logits,
               (const long long*)target, weight, loss_accum, (uint16_t*)dlogits, c, cgan_cs(c), (long)npix);
   CGAN_CHECK_LAUNCH("softmax_ce");
   return CGAN_OK;
@@ -410,10 +555,10 @@ extern "C" int cgan_softmax_ce_nhwc(const void* logits, const int64_t* target, i
 extern "C" int cgan_tv_nhwc(const void* x, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, float weight_h,
                             float weight_w, float* loss_accum, void* dx, void* stream) {
   CGAN_REQUIRE(x && loss_accum && n > 0 && h > 0 && w > 0 && c > 0, "tv: bad arguments");
-  ML_CHECK_DT("tv");
+  LOSS_CHECK_DT("tv");
   const int cs = cgan_cs(c);
   const long total = (long)n * h * w * cs;
-  ML_DISPATCH(dtype, tv_kernel, dim3(grid_ml(total)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, weight_h,
+  LOSS_LAUNCH(dtype, tv_kernel, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, weight_h,
               weight_w, loss_accum, (uint16_t*)dx, h, w, c, cs, total);
   CGAN_CHECK_LAUNCH("tv");
   return CGAN_OK;
@@ -421,9 +566,9 @@ extern "C" int cgan_tv_nhwc(const void* x, int32_t dtype, int32_t n, int32_t h, 
 extern "C" int cgan_entropy_map_nhwc(const void* p, const void* depth, void* y, int32_t dtype, int64_t npix, int32_t c,
                                      void* stream) {
   CGAN_REQUIRE(p && y && npix > 0 && c > 1, "entropy_map: bad arguments");
-  ML_CHECK_DT("entropy_map");
+  LOSS_CHECK_DT("entropy_map");
   const int cs = cgan_cs(c);
-  ML_DISPATCH(dtype, entropy_fwd_kernel, dim3(grid_ml(npix * cs)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)p,
+  LOSS_LAUNCH(dtype, entropy_fwd_kernel, dim3(grid_of(npix * cs)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)p,
               (const uint16_t*)depth, (uint16_t*)y, c, cs, (long)npix * cs);
   CGAN_CHECK_LAUNCH("entropy_map");
   return CGAN_OK;
@@ -431,9 +576,9 @@ extern "C" int cgan_entropy_map_nhwc(const void* p, const void* depth, void* y, 
 extern "C" int cgan_entropy_map_bwd_nhwc(const void* p, const void* depth, const void* dy, void* dp, int32_t dtype,
                                          int64_t npix, int32_t c, void* stream) {
   CGAN_REQUIRE(p && dy && dp && npix > 0 && c > 1, "entropy_map_bwd: bad arguments");
-  ML_CHECK_DT("entropy_map_bwd");
+  LOSS_CHECK_DT("entropy_map_bwd");
   const int cs = cgan_cs(c);
-  ML_DISPATCH(dtype, entropy_bwd_kernel, dim3(grid_ml(npix * cs)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)p,
+  LOSS_LAUNCH(dtype, entropy_bwd_kernel, dim3(grid_of(npix * cs)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)p,
               (const uint16_t*)depth, (const uint16_t*)dy, (uint16_t*)dp, c, cs, (long)npix * cs);
   CGAN_CHECK_LAUNCH("entropy_map_bwd");
   return CGAN_OK;
@@ -442,9 +587,9 @@ extern "C" int cgan_entropy_pair_from_nchw(const float* prob, const float* depth
                                            int32_t c, int32_t h, int32_t w, void* stream) {
   CGAN_REQUIRE(prob && y && n > 0 && h > 0 && w > 0, "entropy_pair_from_nchw: bad arguments");
   CGAN_REQUIRE(c > 1 && c <= ADV_MAXC, "entropy_pair_from_nchw: %d channels (2..%d)", c, ADV_MAXC);
-  ML_CHECK_DT("entropy_pair_from_nchw");
+  LOSS_CHECK_DT("entropy_pair_from_nchw");
   const long npix = (long)n * h * w;
-  ML_DISPATCH(dtype, entropy_pair_nchw_fwd_kernel, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream, prob, depth,
+  LOSS_LAUNCH(dtype, entropy_pair_nchw_fwd_kernel, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream, prob, depth,
               (uint16_t*)y, c, (long)h * w, cgan_cs(2 * c), npix);
   CGAN_CHECK_LAUNCH("entropy_pair_from_nchw");
   return CGAN_OK;
@@ -453,9 +598,9 @@ extern "C" int cgan_entropy_pair_from_nchw_bwd(const float* prob, const float* d
                                                int32_t dtype, int32_t n, int32_t c, int32_t h, int32_t w, void* stream) {
   CGAN_REQUIRE(prob && dy && dprob && n > 0 && h > 0 && w > 0, "entropy_pair_from_nchw_bwd: bad arguments");
   CGAN_REQUIRE(c > 1 && c <= ADV_MAXC, "entropy_pair_from_nchw_bwd: %d channels (2..%d)", c, ADV_MAXC);
-  ML_CHECK_DT("entropy_pair_from_nchw_bwd");
+  LOSS_CHECK_DT("entropy_pair_from_nchw_bwd");
   const long npix = (long)n * h * w;
-  ML_DISPATCH(dtype, entropy_pair_nchw_bwd_kernel, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream, prob, depth,
+  LOSS_LAUNCH(dtype, entropy_pair_nchw_bwd_kernel, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream, prob, depth,
               (const uint16_t*)dy, dprob, c, (long)h * w, cgan_cs(2 * c), npix);
   CGAN_CHECK_LAUNCH("entropy_pair_from_nchw_bwd");
   return CGAN_OK;
@@ -465,13 +610,13 @@ extern "C" int cgan_advent_entropy_pair_nhwc(const void* logits, const void* dep
   CGAN_REQUIRE(logits && y && npix > 0, "advent_entropy_pair: bad arguments");
   CGAN_REQUIRE(sigmoid_pair ? c == 1 : (c > 1 && c <= ADV_MAXC), "advent_entropy_pair: %d channels (softmax: 2..%d, sigmoid pair: 1)",
                c, ADV_MAXC);
-  ML_CHECK_DT("advent_entropy_pair");
+  LOSS_CHECK_DT("advent_entropy_pair");
   const int C = sigmoid_pair ? 2 : c;
   if (sigmoid_pair)
-    ML_DISPATCH2(dtype, advent_pair_fwd_kernel, true, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream,
+    LOSS_LAUNCH2(dtype, advent_pair_fwd_kernel, true, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream,
                  (const uint16_t*)logits, (const uint16_t*)depth, (uint16_t*)y, c, cgan_cs(c), cgan_cs(2 * C), (long)npix);
   else
-    ML_DISPATCH2(dtype, advent_pair_fwd_kernel, false, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream,
+    LOSS_LAUNCH2(dtype, advent_pair_fwd_kernel, false, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream,
                  (const uint16_t*)logits, (const uint16_t*)depth, (uint16_t*)y, c, cgan_cs(c), cgan_cs(2 * C), (long)npix);
   CGAN_CHECK_LAUNCH("advent_entropy_pair");
   return CGAN_OK;
@@ -480,14 +625,14 @@ extern "C" int cgan_advent_entropy_pair_bwd_nhwc(const void* logits, const void*
                                                  int32_t dtype, int64_t npix, int32_t c, int32_t sigmoid_pair, void* stream) {
   CGAN_REQUIRE(logits && dy && dlogits && npix > 0, "advent_entropy_pair_bwd: bad arguments");
   CGAN_REQUIRE(sigmoid_pair ? c == 1 : (c > 1 && c <= ADV_MAXC), "advent_entropy_pair_bwd: %d channels", c);
-  ML_CHECK_DT("advent_entropy_pair_bwd");
+  LOSS_CHECK_DT("advent_entropy_pair_bwd");
   const int C = sigmoid_pair ? 2 : c;
   if (sigmoid_pair)
-    ML_DISPATCH2(dtype, advent_pair_bwd_kernel, true, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream,
+    LOSS_LAUNCH2(dtype, advent_pair_bwd_kernel, true, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream,
                  (const uint16_t*)logits, (const uint16_t*)depth, (const uint16_t*)dy, (uint16_t*)dlogits, c, cgan_cs(c),
                  cgan_cs(2 * C), (long)npix);
   else
-    ML_DISPATCH2(dtype, advent_pair_bwd_kernel, false, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream,
+    LOSS_LAUNCH2(dtype, advent_pair_bwd_kernel, false, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream,
                  (const uint16_t*)logits, (const uint16_t*)depth, (const uint16_t*)dy, (uint16_t*)dlogits, c, cgan_cs(c),
                  cgan_cs(2 * C), (long)npix);
   CGAN_CHECK_LAUNCH("advent_entropy_pair_bwd");
@@ -497,13 +642,13 @@ extern "C" int cgan_minent_nhwc(const void* p, int32_t dtype, int64_t npix, int3
                                 float weight, float* loss_accum, void* dp, float* workspace, void* stream) {
   CGAN_REQUIRE(p && loss_accum && workspace && npix > 0 && c > 1, "minent: bad arguments");
   CGAN_REQUIRE(version == 1 || version == 2, "minent: version must be 1 or 2");
-  ML_CHECK_DT("minent");
+  LOSS_CHECK_DT("minent");
   hipStream_t s = (hipStream_t)stream;
   const int cs = cgan_cs(c);
   const long total = (long)npix * cs;
-  const int rows = grid_ml(total);          // <= CGAN_MINENT_WORKSPACE_FLOATS
-  ML_DISPATCH(dtype, minent_sum_kernel, dim3(rows), dim3(256), 0, s, (const uint16_t*)p, workspace, c, cs, total);
-  ML_DISPATCH(dtype, minent_kernel, dim3(grid_ml(total)), dim3(256), 0, s, (const uint16_t*)p, (const float*)workspace,
+  const int rows = grid_of(total);          // <= CGAN_MINENT_WORKSPACE_FLOATS
+  LOSS_LAUNCH(dtype, minent_sum_kernel, dim3(rows), dim3(256), 0, s, (const uint16_t*)p, workspace, c, cs, total);
+  LOSS_LAUNCH(dtype, minent_kernel, dim3(grid_of(total)), dim3(256), 0, s, (const uint16_t*)p, (const float*)workspace,
               version, lambda_var, weight, 1.f / (float)npix, loss_accum, (uint16_t*)dp, c, cs, total, rows);
   CGAN_CHECK_LAUNCH("minent");
   return CGAN_OK;
@@ -511,8 +656,8 @@ extern "C" int cgan_minent_nhwc(const void* p, int32_t dtype, int64_t npix, int3
 extern "C" int cgan_bce_logits_map_nhwc(const void* x, const float* target, int32_t dtype, int64_t npix, float weight,
                                         float* loss_accum, void* dx, void* stream) {
   CGAN_REQUIRE(x && target && loss_accum && npix > 0, "bce_logits_map: bad arguments");
-  ML_CHECK_DT("bce_logits_map");
-  ML_DISPATCH(dtype, bce_map_kernel, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, target,
+  LOSS_CHECK_DT("bce_logits_map");
+  LOSS_LAUNCH(dtype, bce_map_kernel, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, target,
               weight, loss_accum, (uint16_t*)dx, (long)npix);
   CGAN_CHECK_LAUNCH("bce_logits_map");
   return CGAN_OK;
@@ -520,8 +665,8 @@ extern "C" int cgan_bce_logits_map_nhwc(const void* x, const float* target, int3
 extern "C" int cgan_ground_intersection_nhwc(const void* p, const float* ground, int32_t dtype, int64_t npix, float weight,
                                              float* loss_accum, void* stream) {
   CGAN_REQUIRE(p && ground && loss_accum && npix > 0, "ground_intersection: bad arguments");
-  ML_CHECK_DT("ground_intersection");
-  ML_DISPATCH(dtype, ground_intersection_kernel, dim3(grid_ml(npix)), dim3(256), 0, (hipStream_t)stream,
+  LOSS_CHECK_DT("ground_intersection");
+  LOSS_LAUNCH(dtype, ground_intersection_kernel, dim3(grid_of(npix)), dim3(256), 0, (hipStream_t)stream,
               (const uint16_t*)p, ground, weight, loss_accum, (long)npix);
   CGAN_CHECK_LAUNCH("ground_intersection");
   return CGAN_OK;
@@ -529,9 +674,9 @@ extern "C" int cgan_ground_intersection_nhwc(const void* p, const float* ground,
 extern "C" int cgan_affine_sum_nhwc(const void* x, int32_t dtype, int64_t npix, int32_t c, float a, float b,
                                     float* loss_accum, void* dx, void* stream) {
   CGAN_REQUIRE(x && loss_accum && npix > 0 && c > 0, "affine_sum: bad arguments");
-  ML_CHECK_DT("affine_sum");
+  LOSS_CHECK_DT("affine_sum");
   const int cs = cgan_cs(c);
-  ML_DISPATCH(dtype, affine_sum_kernel, dim3(grid_ml(npix * cs)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, a,
+  LOSS_LAUNCH(dtype, affine_sum_kernel, dim3(grid_of(npix * cs)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, a,
               b, loss_accum, (uint16_t*)dx, c, cs, (long)npix * cs);
   CGAN_CHECK_LAUNCH("affine_sum");
   return CGAN_OK;

@@ -1,5 +1,6 @@
-// Elementwise / reduction kernels of the training path (backward of activations and instance norm, GAN and
-// feature-matching losses with their gradients, spectral-norm weight-gradient transform).  All HBM-bound.
+// Elementwise / reduction kernels of the training path: backward of activations, instance norm, SPADE's elementwise stage
+// and training-mode BatchNorm, spectral-norm weight-gradient transform.  All HBM-bound.  No loss code: every loss term is
+// in losses.hip.
 #include "cgan_common.h"
 
 namespace {
@@ -561,142 +562,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const uint16_t* __res
   }
 }
 
-// ---- losses ---------------------------------------------------------------------------------------------------
-// block-level sum -> one atomic per block
-__device__ __forceinline__ void block_atomic_add(float v, float* dst) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __shared__ float part[4];
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(dst, part[0] + part[1] + part[2] + part[3]);
-}
-
-// nn.BCEWithLogitsLoss against a constant target over the c logical channels of an NHWC tensor:
-// loss += weight * sum(max(x,0) - x t + log1p(exp(-|x|)));  dx = weight * (sigmoid(x) - t) (pad channels 0)
-template <typename T>
-__global__ __launch_bounds__(256) void bce_logits_kernel(const uint16_t* __restrict__ x, float target, float weight,
-                                                         float* __restrict__ loss, uint16_t* __restrict__ dx, int cs,
-                                                         int c, long groups) {
-  const int cg_total = cs / 8;
-  float acc = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const int cg = (int)(i % cg_total);
-    const u32x4 v = reinterpret_cast<const u32x4*>(x)[i];
-    u32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a[2], gr[2];
-      unpack2<T>(v[e], a[0], a[1]);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const bool live = cg * 8 + 2 * e + h < c;
-        const float xv = a[h];
-        const float l = fmaxf(xv, 0.f) - xv * target + log1pf(__expf(-fabsf(xv)));
-        acc += live ? l : 0.f;
-        const float sg = 1.f / (1.f + __expf(-xv));
-        gr[h] = live ? weight * (sg - target) : 0.f;
-      }
-      r[e] = pack2<T>(gr[0], gr[1]);
-    }
-    if (dx) reinterpret_cast<u32x4*>(dx)[i] = r;
-  }
-  block_atomic_add(acc * weight, loss);
-}
-
-// nn.MSELoss against a constant target (GANLoss with use_lsgan=True, climategan/losses.py:50-52) over the c logical channels:
-// loss += weight * sum (x - t)^2;  dx = weight * 2 (x - t) (pad channels 0)
-template <typename T>
-__global__ __launch_bounds__(256) void mse_const_kernel(const uint16_t* __restrict__ x, float target, float weight,
-                                                        float* __restrict__ loss, uint16_t* __restrict__ dx, int cs, int c,
-                                                        long groups) {
-  const int cg_total = cs / 8;
-  float acc = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const int cg = (int)(i % cg_total);
-    const u32x4 v = reinterpret_cast<const u32x4*>(x)[i];
-    u32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a[2], gr[2];
-      unpack2<T>(v[e], a[0], a[1]);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const bool live = cg * 8 + 2 * e + h < c;
-        const float d = a[h] - target;
-        acc += live ? d * d : 0.f;
-        gr[h] = live ? weight * 2.f * d : 0.f;
-      }
-      r[e] = pack2<T>(gr[0], gr[1]);
-    }
-    if (dx) reinterpret_cast<u32x4*>(dx)[i] = r;
-  }
-  block_atomic_add(acc * weight, loss);
-}
-
-// HingeLoss (climategan/losses.py:550-593) over the c logical channels: discriminator side (hinged)
-// loss += weight * sum max(0, 1 - sgn x)   [= -mean(min(sgn x - 1, 0))],  dx = -sgn weight where 1 - sgn x > 0 (half of it
-// on an exact tie, torch.min's rule); generator side (not hinged) loss += weight * sum(-sgn x), dx = -sgn weight
-template <typename T>
-__global__ __launch_bounds__(256) void hinge_kernel(const uint16_t* __restrict__ x, float sgn, int hinged, float weight,
-                                                    float* __restrict__ loss, uint16_t* __restrict__ dx, int cs, int c,
-                                                    long groups) {
-  const int cg_total = cs / 8;
-  float acc = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const int cg = (int)(i % cg_total);
-    const u32x4 v = reinterpret_cast<const u32x4*>(x)[i];
-    u32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a[2], gr[2];
-      unpack2<T>(v[e], a[0], a[1]);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const bool live = cg * 8 + 2 * e + h < c;
-        const float mval = sgn * a[h] - 1.f;                 // min(mval, 0) is what the reference averages
-        float l, g;
-        if (hinged) {
-          l = mval < 0.f ? -mval : 0.f;
-          g = mval < 0.f ? -sgn : (mval == 0.f ? -0.5f * sgn : 0.f);
-        } else {
-          l = -sgn * a[h];
-          g = -sgn;
-        }
-        acc += live ? l : 0.f;
-        gr[h] = live ? weight * g : 0.f;
-      }
-      r[e] = pack2<T>(gr[0], gr[1]);
-    }
-    if (dx) reinterpret_cast<u32x4*>(dx)[i] = r;
-  }
-  block_atomic_add(acc * weight, loss);
-}
-
-// nn.L1Loss pieces: loss += weight * sum|a - b|;  da = weight * sign(a - b)
-template <typename T>
-__global__ __launch_bounds__(256) void l1_kernel(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b,
-                                                 float weight, float* __restrict__ loss, uint16_t* __restrict__ da,
-                                                 long groups) {
-  float acc = 0.f;
-#pragma unroll 2
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const u32x4 va = CGAN_LD_STREAM(reinterpret_cast<const u32x4*>(a) + i);
-    const u32x4 vb = CGAN_LD_STREAM(reinterpret_cast<const u32x4*>(b) + i);
-    u32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a0, a1, b0, b1;
-      unpack2<T>(va[e], a0, a1);
-      unpack2<T>(vb[e], b0, b1);
-      const float d0 = a0 - b0, d1 = a1 - b1;
-      acc += fabsf(d0) + fabsf(d1);
-      r[e] = pack2<T>(d0 > 0.f ? weight : (d0 < 0.f ? -weight : 0.f), d1 > 0.f ? weight : (d1 < 0.f ? -weight : 0.f));
-    }
-    if (da) CGAN_ST_STREAM(r, reinterpret_cast<u32x4*>(da) + i);
-  }
-  block_atomic_add(acc * weight, loss);
-}
-
 // ---- spectral norm: gradient w.r.t. w_bar from the gradient w.r.t. w = w_bar / sigma, sigma = u^T w_bar v ------
 // Deterministic: block b leaves its partial <g, w_bar> in part[b] (plain store); every block of the apply kernel adds the
 // rows in the same fixed order (SN_BWD_ROWS floats from L2) -- no memset, no atomics, run-to-run identical gradients.
@@ -925,61 +790,6 @@ extern "C" int cgan_batchnorm_act_bwd_grouped(const void* x, const void* out, co
   } else if (mask == 0) { BN_BWD_APPLY(0); } else if (mask == 1) { BN_BWD_APPLY(1); } else { BN_BWD_APPLY(2); }
 #undef BN_BWD_APPLY
   CGAN_CHECK_LAUNCH("batchnorm_act_bwd");
-  return CGAN_OK;
-}
-
-extern "C" int cgan_bce_logits_nhwc(const void* x, int32_t dtype, int64_t npix, int32_t c, float target, float weight,
-                                    float* loss_accum, void* dx, void* stream) {
-  CGAN_REQUIRE(x && loss_accum, "bce_logits: null pointer");
-  CGAN_REQUIRE(dtype == CGAN_F16 || dtype == CGAN_BF16, "bce_logits: bad dtype %d", dtype);
-  CGAN_REQUIRE(npix > 0 && c > 0, "bce_logits: bad shape");
-  const int cs = cgan_cs(c);
-  const long groups = npix * (cs / 8);
-  DISPATCH_T(dtype, bce_logits_kernel, dim3(grid_for_n(groups)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
-             target, weight, loss_accum, (uint16_t*)dx, cs, c, groups);
-  CGAN_CHECK_LAUNCH("bce_logits");
-  return CGAN_OK;
-}
-
-extern "C" int cgan_mse_const_nhwc(const void* x, int32_t dtype, int64_t npix, int32_t c, float target, float weight,
-                                   float* loss_accum, void* dx, void* stream) {
-  CGAN_REQUIRE(x && loss_accum, "mse_const: null pointer");
-  CGAN_REQUIRE(dtype == CGAN_F16 || dtype == CGAN_BF16, "mse_const: bad dtype %d", dtype);
-  CGAN_REQUIRE(npix > 0 && c > 0, "mse_const: bad shape");
-  const int cs = cgan_cs(c);
-  const long groups = npix * (cs / 8);
-  DISPATCH_T(dtype, mse_const_kernel, dim3(grid_for_n(groups)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
-             target, weight, loss_accum, (uint16_t*)dx, cs, c, groups);
-  CGAN_CHECK_LAUNCH("mse_const");
-  return CGAN_OK;
-}
-
-extern "C" int cgan_hinge_nhwc(const void* x, int32_t dtype, int64_t npix, int32_t c, int32_t target_is_real,
-                               int32_t for_discriminator, float weight, float* loss_accum, void* dx, void* stream) {
-  CGAN_REQUIRE(x && loss_accum, "hinge: null pointer");
-  CGAN_REQUIRE(dtype == CGAN_F16 || dtype == CGAN_BF16, "hinge: bad dtype %d", dtype);
-  CGAN_REQUIRE(npix > 0 && c > 0, "hinge: bad shape");
-  CGAN_REQUIRE(for_discriminator || target_is_real, "hinge: The generator's hinge loss must be aiming for real");
-  const int cs = cgan_cs(c);
-  const long groups = npix * (cs / 8);
-  DISPATCH_T(dtype, hinge_kernel, dim3(grid_for_n(groups)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
-             target_is_real ? 1.f : -1.f, for_discriminator ? 1 : 0, weight, loss_accum, (uint16_t*)dx, cs, c, groups);
-  CGAN_CHECK_LAUNCH("hinge");
-  return CGAN_OK;
-}
-
-extern "C" int cgan_l1_nhwc(const void* a, const void* b, int32_t dtype, int64_t numel, float weight, float* loss_accum,
-                            void* da, void* stream) {
-  CGAN_REQUIRE(a && b && loss_accum, "l1: null pointer");
-  CGAN_REQUIRE(dtype == CGAN_F16 || dtype == CGAN_BF16, "l1: bad dtype %d", dtype);
-  CGAN_REQUIRE(numel > 0 && (numel % 8) == 0, "l1: numel must be a positive multiple of 8");
-  const long groups = numel / 8;
-  // at most 2048 blocks (one full round of the chip): every block ends in an atomic on the same address, and 8192 of them
-  // were most of this kernel's time on the large VGG / discriminator maps
-  const int l1_grid = grid_for_n(groups) < 2048 ? grid_for_n(groups) : 2048;
-  DISPATCH_T(dtype, l1_kernel, dim3(l1_grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)a,
-             (const uint16_t*)b, weight, loss_accum, (uint16_t*)da, groups);
-  CGAN_CHECK_LAUNCH("l1");
   return CGAN_OK;
 }
 

@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from . import ops
 from . import autograd as ag
-from .autograd import BceLogitsFn, ConvFn, HingeFn, L1Fn, MaxPool2x2Fn
+from .autograd import ConvFn, MaxPool2x2Fn
 from . import norms as _norms
 from .norms import _PackCache
 
@@ -62,10 +62,8 @@ class GANLoss(nn.Module):
     def _one(self, pred, target_is_real):
         pred = _as_nhwc(pred, "GANLoss")
         n = pred.n * pred.h * pred.w * pred.c
-        if self.use_lsgan:
-            from .autograd import MseConstFn
-            return MseConstFn.apply(pred.t, pred.c, self.get_target_value(target_is_real), 1.0 / n)
-        return BceLogitsFn.apply(pred.t, pred.c, self.get_target_value(target_is_real), 1.0 / n)
+        loss = ag.mse_const_loss if self.use_lsgan else ag.bce_logits_loss
+        return loss(pred, self.get_target_value(target_is_real), 1.0 / n)
 
     def __call__(self, input, target_is_real, *args, **kwargs):
         r = rand()
@@ -98,7 +96,7 @@ class HingeLoss(nn.Module):
             assert target_is_real, "The generator's hinge loss must be aiming for real"
         pred = _as_nhwc(input, "HingeLoss")
         n = pred.n * pred.h * pred.w * pred.c
-        return HingeFn.apply(pred.t, pred.c, bool(target_is_real), bool(for_discriminator), 1.0 / n)
+        return ag.hinge_loss(pred, bool(target_is_real), bool(for_discriminator), 1.0 / n)
 
     def __call__(self, input, target_is_real, for_discriminator=True):
         if isinstance(input, list):
@@ -121,7 +119,7 @@ class FeatMatchLoss(nn.Module):
             for j in range(len(pred_fake[i]) - 1):
                 f, r = _as_nhwc(pred_fake[i][j], "FeatMatchLoss"), _as_nhwc(pred_real[i][j], "FeatMatchLoss")
                 n = f.n * f.h * f.w * f.c
-                total = total + L1Fn.apply(f.t, r.t.detach(), f.c, 1.0 / (n * num_D))
+                total = total + ag.l1_loss(f, r, 1.0 / (n * num_D))
         return total
 
 
@@ -242,7 +240,7 @@ class VGGLoss(nn.Module):
         for i in range(len(x_vgg)):
             f, r = x_vgg[i], y_vgg[i]
             n = f.n * f.h * f.w * f.c
-            loss = loss + L1Fn.apply(f.t, r.t, f.c, self.weights[i] / n)
+            loss = loss + ag.l1_loss(f, r, self.weights[i] / n)
         return loss
 
 
@@ -337,7 +335,7 @@ class CustomBCELoss(nn.Module):
     def __call__(self, prediction, target):
         prediction = _as_nhwc(prediction, "CustomBCELoss")
         n = prediction.n * prediction.h * prediction.w * prediction.c
-        return BceLogitsFn.apply(prediction.t, prediction.c, float(target), 1.0 / n)
+        return ag.bce_logits_loss(prediction, float(target), 1.0 / n)
 
 
 class ADVENTAdversarialLoss(nn.Module):

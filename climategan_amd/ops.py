@@ -1381,6 +1381,17 @@ def bce_logits(x: NHWC, target: float, weight: float, loss_accum: torch.Tensor, 
 
 
 @_batch_chunked("x")
+def mse_const(x: NHWC, target: float, weight: float, loss_accum: torch.Tensor, want_grad=True):
+    """loss_accum += weight * sum (x - target)^2 over x's logical channels; returns d(loss)/dx or None."""
+    _need_cuda(x.t, loss_accum)
+    dx = _empty_like(x.t) if want_grad else None
+    lib = _lib.load()
+    _lib.check(lib.cgan_mse_const_nhwc(_ptr(x.t), x.dtype_id, x.n * x.h * x.w, x.c, float(target), float(weight),
+                                       _ptr(loss_accum), _ptr(dx), _stream()), "cgan_mse_const_nhwc")
+    return NHWC(dx, x.c) if want_grad else None
+
+
+@_batch_chunked("x")
 def hinge_loss(x: NHWC, target_is_real: bool, for_discriminator: bool, weight: float, loss_accum: torch.Tensor,
                want_grad=True):
     """loss_accum += weight * sum HingeLoss.loss terms of x's logical channels (reference losses.py:565-579); returns

@@ -86,6 +86,7 @@ def test_sliced_ops_equal_the_single_call(small_limit):
         acc = torch.zeros(1, device="cuda")
         out["l1"] = ops.l1_loss(x, x2, 0.5, acc)
         out["bce"] = ops.bce_logits(x, 1.0, 0.25, acc)
+        out["mse"] = ops.mse_const(x, 1.0, 0.25, acc)
         out["acc"] = acc
         return out
 

@@ -28,7 +28,7 @@ FAMILIES = [     # (family, regex on the kernel name); first match wins
     ("norm forward (stats, apply)", r"instnorm_partial|instnorm_finalize|norm_act_apply|norm_add_act|bn_train_prepare|bn_stats|bn_from_partials"),
     ("norm backward (reduce, finalize, apply)", r"bn_bwd_|in_bwd_"),
     ("activation / pool / resize / pad backward+forward", r"act_bwd|pool|resize_|reflect_pad|eltwise_kernel|add_act|copy_channels|slice_channels|concat"),
-    ("losses + heads", r"l1_kernel|bce_|hinge|softmax|tv_|minent|entropy|ground_|sigm|sobel|median|affine_sum|painter_heads|sigmoid_pair|radix"),
+    ("losses + heads", r"l1_kernel|pointwise_loss|bce_|softmax|tv_|minent|entropy|ground_|sigm|sobel|median|affine_sum|painter_heads|sigmoid_pair|radix"),
     ("spectral norm (power iteration, gradient)", r"^sn_|sn_bwd|sn_w|sn_reduce"),
     ("weight packs", r"pack_|fold_bn"),
     ("layout (NCHW <-> NHWC)", r"nchw|nhwc"),
@@ -46,7 +46,7 @@ CALL_FAMILIES = [   # (family, regex on the C-ABI entry point of bench.py --call
     ("SPADE backward elementwise", r"spade_bwd"),
     ("norm backward (reduce, finalize, apply)", r"instnorm_act_bwd|batchnorm_act_bwd"),
     ("norm forward (stats, apply)", r"instnorm_stats|norm_act_apply|norm_add_act_apply|batchnorm_train_stats|bn_train_prepare|bn_eval"),
-    ("losses + heads", r"bce|hinge|l1_|softmax|tv_|minent|entropy|ground_|sigm|affine_sum|painter_heads|sigmoid_pair|make_m_cond|advent"),
+    ("losses + heads", r"bce|mse_const|hinge|l1_|softmax|tv_|minent|entropy|ground_|sigm|affine_sum|painter_heads|sigmoid_pair|make_m_cond|advent"),
     ("activation / pool / resize / pad backward+forward", r"act_bwd|pool|resize|reflect_pad|eltwise|add_act|copy_channels|slice_channels"),
     ("spectral norm (power iteration, gradient)", r"spectral_norm"),
     ("weight packs", r"pack|fold_bn"),
