@@ -19,6 +19,7 @@ buffer and one copy on a side stream, and the whole batch is then the one launch
 Out of scope: the Logger's display helpers (``decode_segmap_merged_labels``, ...).
 """
 import json
+import os
 import time
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -26,7 +27,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, parallel
 from .transforms import Compose, RawSource, compile_transforms, get_transforms, set_draws
 from .utils import env_to_path
 
@@ -294,18 +295,44 @@ class OmniLoader:
     ``prefetch=1``: batch k + 1 is read and uploaded on a side stream while the consumer works on batch k; the consumer's
     stream waits for the upload's event before the gather, and the side stream for the gather's event before it writes
     the buffers again.  ``prefetch=0``: no thread and no second stream, everything in ``__iter__`` on the current stream.
-    There are no worker processes: each would open the GPU."""
+    There are no worker processes: each would open the GPU.
 
-    def __init__(self, dataset, batch_size, num_workers=0, prefetch=1, shuffle=True, device=None, transform=None):
+    Data parallel: ``batch_size`` is the GLOBAL batch of a step, whatever the world size, so ``len()`` does not
+    depend on it; rank ``rank`` of ``world`` reads ``parallel.shard_range(batch_size, world, rank)`` of every batch
+    (``local_batch_size`` samples) out of ONE permutation that all ranks share.  ``rank=None, world=None``: the process
+    group's when ``parallel.is_distributed()`` -- the generator's seed is then rank 0's draw, broadcast -- else 0 of 1.
+    ``seed(n)`` must be called with the same ``n`` on every rank.  The transform draws stay per rank.  With
+    ``LOCAL_WORLD_SIZE`` in the environment the reader threads are at most ``16 // LOCAL_WORLD_SIZE`` (one at least)."""
+
+    def __init__(self, dataset, batch_size, num_workers=0, prefetch=1, shuffle=True, device=None, transform=None,
+                 rank=None, world=None):
         self.dataset, self.batch_size = dataset, int(batch_size)
+        from_group = rank is None and world is None and parallel.is_distributed()
+        if from_group:
+            rank, world = parallel.rank(), parallel.world()
+        self.rank, self.world = int(rank or 0), int(1 if world is None else world)
+        # this rank's samples of every global batch; a batch the world does not divide is refused here
+        self._first, self.local_batch_size = 0, self.batch_size
+        if (self.rank, self.world) != (0, 1):
+            self._first, self.local_batch_size = parallel.shard_range(self.batch_size, self.world, self.rank)
         self.num_workers = max(0, min(int(num_workers), MAX_WORKERS))
+        if os.environ.get("LOCAL_WORLD_SIZE"):          # the ranks of one machine share its CPUs
+            self.num_workers = min(self.num_workers, max(1, MAX_WORKERS // int(os.environ["LOCAL_WORLD_SIZE"])))
         self.prefetch, self.shuffle = int(bool(prefetch)), shuffle
         self.device = torch.device(device) if device is not None else _device(dataset.device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.transform = transform if transform is not None else compile_transforms(dataset.opts, dataset.mode, dataset.domain)
         self.generator = torch.Generator()
-        self.generator.manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+        seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        if from_group:
+            # one permutation for all ranks: rank 0's draw (every rank still makes its own, so that torch's default
+            # generator moves as it does in one process).  A loader built with an explicit rank / world takes part in no
+            # collective: its caller gives the ranks one seed (``seed(n)``, or ``torch.manual_seed`` before)
+            box = [seed]
+            torch.distributed.broadcast_object_list(box, src=0)
+            seed = int(box[0])
+        self.generator.manual_seed(seed)
         self.last_order = None
         self.times = {"read": 0.0, "stage": 0.0, "transform": 0.0, "batches": 0}     # host seconds, summed
         self._slots = [_Slot(), _Slot()]
@@ -424,11 +451,14 @@ class OmniLoader:
         return self.collate(indices, data)
 
     def batches(self):
-        """The index lists of one epoch: a fresh permutation, cut into full batches"""
+        """The index lists of one epoch: a fresh permutation (``last_order``: the whole of it, the same on every rank), cut
+        into full global batches, of each of which this rank takes its ``local_batch_size`` samples -- the ranks' lists of
+        step k, in rank order, are the list of a one-process loader with the same seed"""
         n = len(self.dataset)
         order = torch.randperm(n, generator=self.generator).tolist() if self.shuffle else list(range(n))
         self.last_order = order
-        return [order[k * self.batch_size:(k + 1) * self.batch_size] for k in range(len(self))]
+        first, per = self._first, self.local_batch_size
+        return [order[k * self.batch_size + first:k * self.batch_size + first + per] for k in range(len(self))]
 
     def __iter__(self):
         self._drain()
@@ -455,10 +485,11 @@ class OmniLoader:
             yield self._finish(indices, staged, self._slots[k % 2])
 
 
-def get_loader(mode, domain, opts, prefetch=1, device=None):
+def get_loader(mode, domain, opts, prefetch=1, device=None, *, rank=None, world=None):
     """reference data.py:506-528: the loader of one mode and domain; ``opts.data.loaders.batch_size`` samples per batch
     (``opts.train.kitti.batch_size`` for the kitti domain while ``train.kitti.pretrain``), shuffled, the last partial batch
-    dropped, ``min(opts.data.loaders.num_workers, 16)`` reader threads."""
+    dropped, ``min(opts.data.loaders.num_workers, 16)`` reader threads.  Either batch size is the global one of a
+    data-parallel run; ``rank`` / ``world`` as ``OmniLoader`` reads them."""
     loaders = opts.data.get("loaders") or {}
     kitti = opts.train.get("kitti") or {}
     if domain != "kitti" or not kitti.get("pretrain") or not kitti.get("batch_size"):
@@ -466,7 +497,7 @@ def get_loader(mode, domain, opts, prefetch=1, device=None):
     else:
         batch_size = kitti.get("batch_size", 4)
     return OmniLoader(OmniListDataset(mode, domain, opts, device=device), batch_size,
-                      num_workers=loaders.get("num_workers", 8), prefetch=prefetch, device=device)
+                      num_workers=loaders.get("num_workers", 8), prefetch=prefetch, device=device, rank=rank, world=world)
 
 
 def loader_domains(opts):
@@ -493,7 +524,7 @@ def listed_files(opts):
             for domain in loader_domains(opts) if domain in files[mode]]
 
 
-def get_all_loaders(opts, prefetch=1, device=None):
+def get_all_loaders(opts, prefetch=1, device=None, *, rank=None, world=None):
     """reference data.py:531-539: ``{mode: {domain: loader}}`` for the modes and domains listed in ``opts.data.files``"""
     loaders = {}
     for mode in ["train", "val"]:
@@ -501,5 +532,5 @@ def get_all_loaders(opts, prefetch=1, device=None):
         if mode in opts.data.files:
             for domain in loader_domains(opts):
                 if domain in opts.data.files[mode]:
-                    loaders[mode][domain] = get_loader(mode, domain, opts, prefetch, device)
+                    loaders[mode][domain] = get_loader(mode, domain, opts, prefetch, device, rank=rank, world=world)
     return loaders

@@ -36,6 +36,12 @@ by an event and before ``finish()``'s copy-back by another -- the path a host wi
 
 ``broadcast_parameters`` makes replicas identical at start (parameters AND buffers, incl. the spectral-norm ``u``/``v``
 vectors, which are parameters with ``requires_grad=False``).
+
+The train command's part: ``init_from_env`` / ``shutdown`` open and close the group the launcher describes in
+the environment; ``rank`` / ``world`` / ``is_main`` / ``barrier`` answer for one process when there is no group;
+``broadcast_buffers`` makes rank 0's BatchNorm statistics everybody's at the end of an epoch; ``gather_in_order`` and
+``mean_over_ranks`` make the sharded evaluation's result identical on every rank; ``agree`` stops ranks whose loaders
+or tasks differ before the first gradient collective.
 """
 import os
 from typing import List
@@ -73,6 +79,124 @@ def broadcast_parameters(module: torch.nn.Module, src: int = 0) -> None:
         return
     for t in list(module.parameters()) + list(module.buffers()):
         dist.broadcast(t.data, src=src)
+
+
+def broadcast_buffers(module: torch.nn.Module, src: int = 0) -> None:
+    """Rank ``src``'s buffers (the BatchNorm running statistics: per rank during an epoch, there is no SyncBN) to every
+    rank: stock DDP's ``broadcast_buffers`` convention, called by ``Trainer.train()`` once per epoch -- before the
+    evaluation and the checkpoint -- instead of once per forward.  The buffers' version counters are bumped, so nothing
+    packed from the old values is used again (``ops.touch``)."""
+    if not is_distributed():
+        return
+    buffers = list(module.buffers())
+    for t in buffers:
+        dist.broadcast(t.data, src=src)
+    from . import ops
+    ops.touch(*buffers)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The process group of ``python -m climategan_amd.train`` (DESIGN 6) and the few collectives of its loop that are not the
+# gradient exchange.  Without a group every helper is a plain function of one process: rank 0 of 1, no collective.
+# ----------------------------------------------------------------------------------------------------------------------
+def _has_group() -> bool:
+    return dist.is_available() and dist.is_initialized()
+
+
+def rank() -> int:
+    return dist.get_rank() if _has_group() else 0
+
+
+def world() -> int:
+    return dist.get_world_size() if _has_group() else 1
+
+
+def is_main() -> bool:
+    """Whether this process owns the run's side effects: the run directory, ``opts.yaml``, the checkpoints, the printed
+    tables (rank 0; the only process without a group)"""
+    return rank() == 0
+
+
+def barrier() -> None:
+    if _has_group():
+        dist.barrier()
+
+
+def init_from_env(backend: str = "nccl", timeout_s=None):
+    """The default process group from what ``torch.distributed.run`` sets: ``RANK``, ``WORLD_SIZE``, ``LOCAL_RANK``,
+    ``MASTER_ADDR``, ``MASTER_PORT`` (the last two are read by torch's ``env://`` rendezvous).  Returns (rank, world).
+    Without ``WORLD_SIZE`` nothing happens and the answer is (0, 1).  With it this process takes GPU ``LOCAL_RANK`` --
+    refused when the machine has no such device -- and joins the group, also a group of one (``--nproc-per-node 1``)."""
+    if "WORLD_SIZE" not in os.environ:
+        return 0, 1
+    import datetime
+
+    size, rk = int(os.environ["WORLD_SIZE"]), int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    devices = torch.cuda.device_count()
+    if local >= devices:
+        raise RuntimeError("init_from_env: LOCAL_RANK %d, but this machine has %d GPUs (one process per GPU: "
+                           "--nproc-per-node must not exceed the device count)" % (local, devices))
+    torch.cuda.set_device(local)
+    kwargs = {} if timeout_s is None else {"timeout": datetime.timedelta(seconds=float(timeout_s))}
+    if backend == "nccl":
+        kwargs["device_id"] = torch.device("cuda", local)       # the communicator is bound to this rank's GPU at once
+    dist.init_process_group(backend, rank=rk, world_size=size, **kwargs)
+    return rk, size
+
+
+def shutdown() -> None:
+    """Leave the process group, if there is one (``train.main``'s ``finally``)"""
+    if _has_group():
+        dist.destroy_process_group()
+
+
+def gather_in_order(indexed_values):
+    """``[(index, value), ...]`` of this rank -> the values of ALL ranks, sorted by index, the same list on every rank
+    (``eval_images``: rank r scores the display images r, r + world, ...; the table is then averaged in image order
+    whatever the world size).  A rank with nothing contributes ``[]``.  Without a group: this rank's values by index."""
+    mine = [(int(i), v) for i, v in indexed_values]
+    if _has_group():
+        parts = [None] * world()
+        dist.all_gather_object(parts, mine)
+        mine = [pair for part in parts for pair in part]
+    return [v for _, v in sorted(mine, key=lambda pair: pair[0])]
+
+
+def mean_over_ranks(values: dict) -> dict:
+    """{key: float} -> {key: mean of the ranks' values}, summed in rank order on the host: bit-identical on every rank.
+    Every rank must hold the same keys (they are the logged terms of the same model and tasks)."""
+    if not _has_group():
+        return dict(values)
+    parts = [None] * world()
+    dist.all_gather_object(parts, {k: float(v) for k, v in values.items()})
+    for r, part in enumerate(parts):
+        if set(part) != set(parts[0]):
+            raise RuntimeError("mean_over_ranks: rank %d holds the entries %s, rank 0 holds %s"
+                               % (r, sorted(part), sorted(parts[0])))
+    return {k: sum(part[k] for part in parts) / len(parts) for k in parts[0]}
+
+
+def agree(name: str, value):
+    """Every rank must hold the same ``value`` (anything picklable; compared with ``==``): gathered from all ranks, and a
+    difference raises on EVERY rank, naming ``name``, the first differing entry of a dict and the two ranks -- before
+    the ranks can reach different collectives (unequal step counts: DESIGN 6).  Returns ``value``."""
+    if not _has_group():
+        return value
+    parts = [None] * world()
+    dist.all_gather_object(parts, value)
+    for r, other in enumerate(parts):
+        if other == parts[0]:
+            continue
+        entry, a, b = "", parts[0], other
+        if isinstance(a, dict) and isinstance(b, dict):
+            for key in sorted(set(a) | set(b), key=repr):
+                if a.get(key, "<missing>") != b.get(key, "<missing>"):
+                    entry, a, b = " entry %r:" % (key,), a.get(key, "<missing>"), b.get(key, "<missing>")
+                    break
+        raise ValueError("parallel.agree: %s differs across ranks:%s %r on rank 0, %r on rank %d"
+                         % (name, entry, a, b, r))
+    return value
 
 
 class _EventWork:

@@ -2,7 +2,20 @@
 run directory out.
 
     python -m climategan_amd.train [--config FILE.yaml] [--resume RUN_DIR] [--output RUN_DIR] [--dtype bf16|fp16]
-                                   [key.sub=value ...]
+                                   [--backend nccl|gloo] [--dist-timeout SECONDS] [--seed N] [key.sub=value ...]
+
+Data parallel, one process per GPU -- the program goes after the launcher's own options, and the launcher
+starts every rank as a fresh process:
+
+    python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m climategan_amd.train --config FILE.yaml
+
+``main()`` reads the launcher's environment (``parallel.init_from_env``: ``RANK``, ``WORLD_SIZE``, ``LOCAL_RANK``,
+``MASTER_ADDR``, ``MASTER_PORT``; without ``WORLD_SIZE`` this is one process and none of the following applies).
+``data.loaders.batch_size`` is the GLOBAL batch per domain and step, of which every rank reads its equal share, so the
+steps per epoch, the schedulers and ``global_step`` do not depend on the number of GPUs.  Rank 0 alone creates the run
+directory, writes ``opts.yaml`` and the checkpoints and prints the tables; ``--resume`` reads the same file on every
+rank.  ``--seed N`` seeds ``random``, numpy and torch with ``N`` before the setup on every rank (the same initial model)
+and with ``N + 1 + rank`` after it (augmentation draws and label noise differ across ranks, reproducibly).
 
 The options are ``config.default_opts()`` with the loop's part of ``shared/trainer/defaults.yaml`` (``train_defaults``),
 then the ``--config`` file, then the dotted overrides, whose values are read by ``yaml.safe_load`` (``train.epochs=2``,
@@ -33,6 +46,7 @@ REFUSED = {
 }
 ALLOWED = ("comet.display_size",)
 DTYPES = ("bf16", "fp16")
+BACKENDS = ("nccl", "gloo")
 
 
 def train_defaults():
@@ -133,6 +147,12 @@ def parse_args(argv=None):
     parser.add_argument("--output", default=None, metavar="RUN_DIR", help="the run directory (sets output_path)")
     parser.add_argument("--dtype", default=None, choices=DTYPES,
                         help="the kernels' 16-bit type (default: bf16, or fp16 with train.amp)")
+    parser.add_argument("--backend", default="nccl", choices=BACKENDS,
+                        help="the process group's backend in a data-parallel run (nccl is RCCL on ROCm)")
+    parser.add_argument("--dist-timeout", default=None, type=float, metavar="SECONDS",
+                        help="the process group's timeout (default: torch's own)")
+    parser.add_argument("--seed", default=None, type=int, metavar="N",
+                        help="seed random, numpy and torch: N before the setup on every rank, N + 1 + rank after it")
     parser.add_argument("overrides", nargs="*", metavar="key.sub=value", help="dotted overrides, values in yaml syntax")
     args = parser.parse_args(argv)
     for arg in args.overrides:
@@ -140,39 +160,63 @@ def parse_args(argv=None):
     return args
 
 
+def seed_everything(n):
+    """``random``, numpy's and torch's global generators (torch's: the host's and every GPU's)"""
+    import random
+
+    import numpy as np
+    import torch
+    random.seed(n)
+    np.random.seed(n)
+    torch.manual_seed(n)
+
+
 def main(argv=None):
     args = parse_args(argv)
     import torch
 
+    from . import parallel
     from .trainer import Trainer
 
-    if args.resume is not None:
-        overrides = build_opts(args.config, args.overrides, base={})
-        if args.output is not None:
-            overrides["output_path"] = str(args.output)
-        trainer = Trainer.resume_from_path(args.resume, overrides=plain(overrides), inference=False)
-        opts = trainer.opts
-    else:
-        opts = build_opts(args.config, args.overrides)
-        if args.output is not None:
-            opts.output_path = str(args.output)
-        if not (opts.get("data") or {}).get("files"):
-            raise SystemExit("train: no file lists -- set data.files.base and data.files.train / val (--config or overrides)")
-        run_dir = Path(opts.output_path)
-        run_dir.mkdir(parents=True, exist_ok=True)
-        (run_dir / "opts.yaml").write_text(yaml.safe_dump(plain(opts)))
-        trainer = Trainer(opts).setup()
-    if args.dtype is not None:
-        dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
-        trainer.G.set_compute_dtype(dtype)
-        trainer.D.set_compute_dtype(dtype)
-    print("train: %d epochs into %s" % (int(opts.train.epochs), opts.output_path))
+    rank, _world = parallel.init_from_env(args.backend, args.dist_timeout)
+    trainer = None
     try:
+        if args.seed is not None:           # the same initial model and the same permutations on every rank
+            seed_everything(args.seed)
+        device = torch.device("cuda", torch.cuda.current_device()) if parallel.world() > 1 else None
+        if args.resume is not None:
+            overrides = build_opts(args.config, args.overrides, base={})
+            if args.output is not None:
+                overrides["output_path"] = str(args.output)
+            trainer = Trainer.resume_from_path(args.resume, overrides=plain(overrides), inference=False, device=device)
+            opts = trainer.opts
+        else:
+            opts = build_opts(args.config, args.overrides)
+            if args.output is not None:
+                opts.output_path = str(args.output)
+            if not (opts.get("data") or {}).get("files"):
+                raise SystemExit("train: no file lists -- set data.files.base and data.files.train / val (--config or overrides)")
+            if parallel.is_main():          # the run directory and its opts.yaml are rank 0's; nobody reads them early
+                run_dir = Path(opts.output_path)
+                run_dir.mkdir(parents=True, exist_ok=True)
+                (run_dir / "opts.yaml").write_text(yaml.safe_dump(plain(opts)))
+            parallel.barrier()
+            trainer = Trainer(opts, device=device).setup()
+        if args.seed is not None:           # augmentation draws and label noise: different per rank, reproducible
+            seed_everything(args.seed + 1 + rank)
+        if args.dtype is not None:
+            dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
+            trainer.G.set_compute_dtype(dtype)
+            trainer.D.set_compute_dtype(dtype)
+        if parallel.is_main():
+            print("train: %d epochs into %s" % (int(opts.train.epochs), opts.output_path))
         trainer.train()
     finally:
-        for mode_dict in (trainer.all_loaders or {}).values():
-            for loader in mode_dict.values():
-                loader.close()
+        if trainer is not None:
+            for mode_dict in (trainer.all_loaders or {}).values():
+                for loader in mode_dict.values():
+                    loader.close()
+        parallel.shutdown()
     return 0
 
 

@@ -178,6 +178,14 @@ class Trainer:
             self.loaders = {mode: {domain: loader for domain, loader in mode_dict.items() if domain != "kitti"}
                             for mode, mode_dict in self.all_loaders.items()}
             self.set_display_images()
+        if is_distributed():
+            # ranks whose step counts differ would wait on different collectives: stopped here, on every rank, before
+            # the first gradient exchange
+            from .parallel import agree
+            agree("opts.tasks", list(o.tasks))
+            agree("the loaders' (len(dataset), batch_size)",
+                  {(mode, domain): (len(loader.dataset), loader.batch_size)
+                   for mode, mode_dict in (self.all_loaders or {}).items() for domain, loader in mode_dict.items()})
         if os.environ.get("CGAN_GC_FREEZE", "0") == "1":
             self.freeze_host_objects()
         self.is_setup = True
@@ -919,17 +927,29 @@ class Trainer:
         """reference trainer.py:888-922: for ``opts.train.epochs`` epochs ``run_epoch()``, ``run_evaluation()``, ``save()``
         (the pl4m check is ``run_epoch``'s; the kitti and pseudo-label switches are refused by ``setup``).  ``run_epoch``
         has counted the epoch when ``save`` runs: a checkpoint's ``epoch`` is the number of finished epochs.  One line per
-        epoch; returns the list of ``run_evaluation``'s results."""
+        epoch; returns the list of ``run_evaluation``'s results.
+
+        Data parallel: the parameters are in lock-step through the reducers, the BatchNorm statistics are per
+        rank during the epoch; at its end rank 0's buffers become every rank's, so that all ranks evaluate the same model
+        and the checkpoint -- written by rank 0 alone, with a barrier behind it -- is the model that was evaluated.  The
+        epoch's line is rank 0's."""
+        from . import parallel
         assert self.is_setup
         results = []
         for _ in range(int(self.opts.train.epochs)):
             start, step = time.perf_counter(), self.global_step
             last = self.run_epoch()
+            if parallel.is_distributed():
+                parallel.broadcast_buffers(self.G)
+                parallel.broadcast_buffers(self.D)
             results.append(self.run_evaluation())
-            self.save()
+            if parallel.is_main():
+                self.save()
+            parallel.barrier()
             g, d = (float(last[0]), float(last[1])) if last is not None else (float("nan"), float("nan"))
-            print("epoch %d: %d steps in %.1f s, last G loss %.4f, last D loss %.4f"
-                  % (self.epoch - 1, self.global_step - step, time.perf_counter() - start, g, d))
+            if parallel.is_main():
+                print("epoch %d: %d steps in %.1f s, last G loss %.4f, last D loss %.4f"
+                      % (self.epoch - 1, self.global_step - step, time.perf_counter() - start, g, d))
         return results
 
     # ------------------------------------------------------------------------------------------ validation
@@ -967,7 +987,13 @@ class Trainer:
         validation loaders, each tuple keyed by domain): eval mode, ``get_G_loss`` per batch with the logged generator terms
         AVERAGED over the batches (sum_dict / div_dict, trainer.py:1674-1679), then ``eval_images("val", d)`` for d in r, s when the Masker has an
         m or s task, train mode again.  Comet image panels and the validation FID (logger.py, fid.py) are outside this
-        path.  Returns {"losses": averaged terms, "metrics": {domain: eval_images' table}}."""
+        path.  Returns {"losses": averaged terms, "metrics": {domain: eval_images' table}}.
+
+        Data parallel, without arguments: the loaders give this rank's share of each validation batch, the averaged terms
+        are then averaged over the ranks (``parallel.mean_over_ranks``), and ``eval_images`` shares the display images out;
+        the result is the same dict on every rank.  Every rank must make the call."""
+        from . import parallel
+        sharded = val_batches is None and parallel.is_distributed()     # batches a caller hands over are its own affair
         if val_batches is None:
             val_batches = self._multi_domain_batches(self.val_loaders, False)
         self.eval_mode()
@@ -980,6 +1006,10 @@ class Trainer:
                     sums[k] = sums.get(k, 0.0) + float(v)
             n += 1
         losses = {k: v / max(n, 1) for k, v in sums.items()}
+        if sharded:
+            # every rank has averaged its equal share of each global validation batch: the mean over the ranks is the mean
+            # over the global batches, and the same numbers on every rank
+            losses = parallel.mean_over_ranks(losses)
         metrics = {}
         if display_images is not None:
             self.display_images = display_images
@@ -998,7 +1028,10 @@ class Trainer:
         as the reference does), per task m (binarised mask at 0.5; the 1-channel accuracy quirk of eval_metrics.py:67-76
         kept) and s (segmentation logits); the counts behind both metrics come from one HIP pass over the device tensors
         (``cgan_seg_counts``), nothing is moved to the host.  The averaged table is printed (the reference logs it to comet
-        when an experiment exists), kept in ``self.last_metrics[(mode, domain)]``; returns 0 like the reference."""
+        when an experiment exists), kept in ``self.last_metrics[(mode, domain)]``; returns 0 like the reference.
+
+        Data parallel: a collective call -- every rank makes it, scores its share of the images, and holds the one-process
+        table afterwards; rank 0 prints it."""
         import numpy as np
 
         from . import functional as Fn
@@ -1022,7 +1055,31 @@ class Trainer:
         for task in scores:
             for key in metric_funcs:
                 scores[task][key] = []
-        for im_set in images[mode][domain]:
+        # data parallel: rank r scores the images r, r + world, ...; the per-image values of all ranks are then
+        # put back into image order, so the table below is the one a single process computes, on every rank
+        from . import parallel
+        sharded = parallel.is_distributed()
+        todo = list(enumerate(images[mode][domain]))
+        n_images, mask_forwards = len(todo), 0
+        if sharded:
+            todo = todo[parallel.rank()::parallel.world()]
+
+        def skip_mask_forwards(upto):
+            """Evaluation is not free of side effects: every forward of the mask decoder is one power iteration of its
+            spectral-norm u / v, eval mode included (norms.py, as the reference), so image i is scored after i + 1 of
+            them.  The iteration reads the weights alone, not the image: a rank makes the iterations of the images the
+            other ranks score without their forwards -- image i sees the state it sees in one process, and every rank
+            leaves with the same u / v (they are parameters: the replicas stay in lock-step)."""
+            nonlocal mask_forwards
+            if sharded and "m" in self.opts.tasks:
+                from .norms import spectral_norm_step_all
+                for _ in range(upto - mask_forwards):
+                    spectral_norm_step_all(self.G.decoders["m"], self.G.compute_dtype)
+                mask_forwards = upto
+
+        for index, im_set in todo:
+            skip_mask_forwards(index)
+            mask_forwards += 1
             data = im_set["data"]
             x = data["x"].unsqueeze(0).to(self.device)
             z = self.G.encode(x)
@@ -1033,7 +1090,7 @@ class Trainer:
                 s_pred = Fn.to_nchw(self.G.decoders["s"].forward_nhwc(z, z_depth))
                 s = data["s"].unsqueeze(0).to(self.device)
                 for name, fn in metric_funcs.items():
-                    scores["s"][name].append(fn(s_pred, s))
+                    scores["s"][name].append((index, fn(s_pred, s)))
             if "m" in self.opts.tasks:
                 if z_depth is None and self.opts.gen.m.use_dada and "d" in self.opts.tasks:
                     _, z_depth = self.G.decoders["d"].forward_nhwc(z)
@@ -1042,17 +1099,23 @@ class Trainer:
                 pred_mask = (self.G.mask(x=x, z=z, cond=None, z_depth=z_depth) > 0.5).to(torch.float32)
                 pred_prob = torch.cat([1 - pred_mask, pred_mask], dim=1)
                 m = data["m"].unsqueeze(0).to(self.device)
-                scores["m"]["accuracy"].append(accuracy(pred_mask, m))
-                scores["m"]["mIOU"].append(mIOU(pred_prob, m))
+                scores["m"]["accuracy"].append((index, accuracy(pred_mask, m)))
+                scores["m"]["mIOU"].append((index, mIOU(pred_prob, m)))
+        skip_mask_forwards(n_images)
         table = {}
         for task, met in scores.items():
             table[task] = {}
-            for name, values in met.items():
+            for name, pairs in met.items():
+                if sharded:
+                    values = parallel.gather_in_order([(i, float(v)) for i, v in pairs])
+                else:
+                    values = [v for _, v in pairs]
                 v = float(np.mean(values)) if values else float("nan")
                 table[task][name] = v if not np.isnan(v) else -1
         self.last_metrics[(mode, domain)] = table
-        print(f"metrics_{mode}_{domain}")
-        print(flatten_opts(table))
+        if parallel.is_main():
+            print(f"metrics_{mode}_{domain}")
+            print(flatten_opts(table))
         return 0
 
     # ------------------------------------------------------------------------------------------ checkpoints
@@ -1190,6 +1253,15 @@ class Trainer:
         self.global_step = checkpoint["step"]
         if self.global_step % 2 != 0:
             self.global_step += 1
+        # data parallel: every rank has read the same file; the broadcast makes "the same" certain for the replicas
+        from .parallel import broadcast_parameters, is_distributed
+        if is_distributed():
+            broadcast_parameters(self.G)
+            if self.D is not None:
+                broadcast_parameters(self.D)
+            ops.touch(*self.G.parameters(), *self.G.buffers())
+            if self.D is not None:
+                ops.touch(*self.D.parameters(), *self.D.buffers())
 
     # ------------------------------------------------------------------------------------------ events
     def compute_flood(self, x, z=None, z_depth=None, m=None, s=None, cloudy=None, bin_value=-1):
