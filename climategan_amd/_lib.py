@@ -259,6 +259,12 @@ _SIGNATURES = {
     "cgan_png_encode_u8": (C.c_int, [_P] + [C.c_int32] * 4 + [_P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     "cgan_png_encode_u8_level": (C.c_int, [_P] + [C.c_int32] * 5 + [_P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     "cgan_png_huffman_lengths": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "cgan_jpeg_bound_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "cgan_jpeg_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "cgan_jpeg_encode_u8": (C.c_int, [_P] + [C.c_int32] * 6 + [_P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "cgan_jpeg_coefficients_u8": (C.c_int, [_P] + [C.c_int32] * 6 + [_P, _P]),
+    "cgan_jpeg_tables": (C.c_int, [C.c_int32, _P, _P]),
+    "cgan_jpeg_scan_host": (C.c_int, [_P] + [C.c_int32] * 5 + [_P, C.c_size_t, _P]),
     "cgan_smog_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "cgan_smog_nchw": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), _P, C.c_size_t, _P]),

@@ -13,7 +13,9 @@ only compressed bytes come back to the host.
 Differences: ``--upload`` (comet) is refused; an existing output directory without ``--overwrite`` is refused with a
 message instead of the reference's ``input()`` prompt, which nobody answers in a batch job; images are read, inferred and
 written batch by batch rather than all held in memory; ``--dtype`` selects the kernels' 16-bit type; ``--png_level 2`` asks
-the device PNG encoder for smaller files (same pixels; neither is an option of the reference's script).
+the device PNG encoder for smaller files (same pixels; neither is an option of the reference's script); ``--format jpg``
+writes the events and the input picture as baseline JPEG files from the device encoder (``jpeg.write``, DESIGN 4.19;
+``--jpeg_quality``, ``--jpeg_subsampling``) -- several times smaller, lossy; the masks stay PNG.
 """
 import argparse
 import shutil
@@ -85,12 +87,17 @@ EVENT_ORDER = ("flood", "wildfire", "smog", "mask", "input")       # the order i
 
 class _Args(argparse.Namespace):
     """``png_level`` is 1 unless the command line gives it: an attribute with a class default, so that the namespace of a
-    run without it -- what ``main`` prints under "Using args" -- holds the entries it held before the option existed."""
+    run without it -- what ``main`` prints under "Using args" -- holds the entries it held before the option existed.  The
+    same for ``format`` and the two JPEG options."""
     png_level = 1
+    format = "png"
+    jpeg_quality = 90
+    jpeg_subsampling = "444"
 
 
 def parse_args(argv=None):
-    """apply_events.py:4-148 (same names, short forms, defaults and help) + ``--dtype`` and ``--png_level``."""
+    """apply_events.py:4-148 (same names, short forms, defaults and help) + ``--dtype``, ``--png_level``, ``--format`` and
+    the two ``--jpeg_*`` options."""
     argv = list(sys.argv[1:] if argv is None else argv)
     for a in argv:
         key = a.split("=", 1)[0]
@@ -136,7 +143,20 @@ def parse_args(argv=None):
                         help="Not an option of the reference's script: the device PNG encoder's level. 1: fixed-Huffman "
                         "blocks; 2: per row the smallest of a fixed, dynamic or stored block (smaller files, same pixels). "
                         "Defaults to 1")
+    parser.add_argument("--format", default=argparse.SUPPRESS, choices=("png", "jpg"),
+                        help="Not an option of the reference's script: the file format of the events and of the input "
+                        "picture. jpg: baseline JPEG from the device encoder (lossy, several times smaller); the masks stay "
+                        "PNG. Defaults to png")
+    parser.add_argument("--jpeg_quality", type=int, default=argparse.SUPPRESS,
+                        help="With --format jpg: libjpeg's quality scale, 1 to 100. Defaults to 90")
+    parser.add_argument("--jpeg_subsampling", default=argparse.SUPPRESS, choices=("444", "420"),
+                        help="With --format jpg: chroma at full resolution (444) or halved both ways (420). Defaults to 444")
     args = parser.parse_args(argv, namespace=_Args())
+    given = vars(args)
+    if args.format != "jpg" and ("jpeg_quality" in given or "jpeg_subsampling" in given):
+        parser.error("--jpeg_quality and --jpeg_subsampling need --format jpg")
+    if not 1 <= args.jpeg_quality <= 100:
+        parser.error("--jpeg_quality must be between 1 and 100")
     if args.batch_size < 1:
         parser.error("--batch_size must be positive")
     if args.zip_outdir and args.output_path is None:
@@ -257,10 +277,10 @@ def read_image(path):
     return a if a.shape[2] == 3 else rgba_to_rgb(a)
 
 
-def event_file_name(stem, event, width, keep_ratio, no_cloudy):
-    """apply_events.py:590-616."""
+def event_file_name(stem, event, width, keep_ratio, no_cloudy, ext="png"):
+    """apply_events.py:590-616; ``ext``: "jpg" for the files ``--format jpg`` writes."""
     suffix = ("_AR" if keep_ratio else "") + ("_no_cloudy" if no_cloudy else "")
-    return "%s_%s_%s%s.png" % (stem, event, width, suffix)
+    return "%s_%s_%s%s.%s" % (stem, event, width, suffix, ext)
 
 
 def get_git_revision_hash():
@@ -312,7 +332,7 @@ def main(argv=None):
                              max_im_width, target_size, bin_value, cloudy)
 
     import_time = time.time()
-    from . import png
+    from . import jpeg, png
     from .bn_fusion import bn_fuse
     from .eval_masker import find_images
     from .trainer import Timer, Trainer
@@ -361,8 +381,13 @@ def main(argv=None):
             with timed("write"):
                 width = x.shape[-1]
                 for event, im_u8 in events_to_uint8(events, x, args.save_input).items():
-                    png.write(im_u8, [outdir / event_file_name(Path(p).stem, event, width, keep_ratio, args.no_cloudy)
-                                      for p in paths], level=args.png_level)
+                    as_jpeg = args.format == "jpg" and event != "mask"         # a binary mask must not be lossy
+                    names = [outdir / event_file_name(Path(p).stem, event, width, keep_ratio, args.no_cloudy,
+                                                      "jpg" if as_jpeg else "png") for p in paths]
+                    if as_jpeg:
+                        jpeg.write(im_u8, names, quality=args.jpeg_quality, subsampling=args.jpeg_subsampling)
+                    else:
+                        png.write(im_u8, names, level=args.png_level)
 
     if args.zip_outdir:
         print("\n\u2022 Zipping output directory... ", end="", flush=True)

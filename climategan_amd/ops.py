@@ -685,6 +685,72 @@ def png_encode(img_u8: torch.Tensor, level: int = 1):
     return buf, sizes
 
 
+JPEG_MAX_WIDTH = 4096        # the widest image cgan_jpeg_encode_u8 takes (pixels, grey or RGB)
+JPEG_SUBSAMPLINGS = ("444", "420")
+
+
+def _jpeg_args(what, img_u8, quality, subsampling):
+    """Refuses what the JPEG entry points do not take, before any launch -> (n, h, w, c, quality, subsampling as int)."""
+    _need_cuda(img_u8)
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise RuntimeError("%s: quality %r: an integer from 1 to 100 expected" % (what, quality))
+    if str(subsampling) not in JPEG_SUBSAMPLINGS:
+        raise RuntimeError("%s: subsampling %r: '444' or '420' expected" % (what, subsampling))
+    if img_u8.dtype != torch.uint8:
+        raise RuntimeError("%s: uint8 input expected, got %s" % (what, img_u8.dtype))
+    if img_u8.dim() != 4 or img_u8.shape[3] not in (1, 3):
+        raise RuntimeError("%s: [N, H, W, C] with C = 1 (grey) or 3 (RGB) expected, got %s" % (what, tuple(img_u8.shape)))
+    if not img_u8.is_contiguous():
+        raise RuntimeError("%s: a contiguous tensor is expected (strides %s)" % (what, img_u8.stride()))
+    n, h, w, c = img_u8.shape
+    if w > JPEG_MAX_WIDTH:
+        raise RuntimeError("%s: width %d exceeds the %d pixels the encoder supports" % (what, w, JPEG_MAX_WIDTH))
+    if n < 1 or h < 1 or w < 1:
+        raise RuntimeError("%s: empty input %s" % (what, tuple(img_u8.shape)))
+    return n, h, w, c, quality, int(str(subsampling))
+
+
+def jpeg_bound_bytes(h: int, w: int, c: int, subsampling="444") -> int:
+    """The most bytes the JPEG file of one [h, w, c] image can have (``jpeg_encode``'s row pitch)."""
+    bound = _lib.load().cgan_jpeg_bound_bytes(int(h), int(w), int(c), int(str(subsampling)))
+    if bound == 0:
+        _lib.check(-1, "cgan_jpeg_bound_bytes")
+    return bound
+
+
+def jpeg_encode(img_u8: torch.Tensor, quality: int = 90, subsampling="444"):
+    """uint8 [N, H, W, C] device tensor (contiguous, C = 1 grey or 3 RGB, W <= JPEG_MAX_WIDTH) -> (buf uint8 [N, bound],
+    sizes int64 [N]): ``buf[i, :sizes[i]]`` is the complete baseline JPEG file of image i.  Both stay on the
+    device and nothing is synchronised; everything else is refused here, before any launch.  ``quality`` 1 .. 100 (libjpeg's
+    scale); ``subsampling`` "444" or "420" (chroma at half resolution both ways; no difference for grey)."""
+    n, h, w, c, quality, sub = _jpeg_args("jpeg_encode", img_u8, quality, subsampling)
+    lib = _lib.load()
+    bound = jpeg_bound_bytes(h, w, c, sub)
+    nbytes = lib.cgan_jpeg_workspace_bytes(n, h, w, c, sub)
+    if nbytes == 0:
+        _lib.check(-1, "cgan_jpeg_workspace_bytes")
+    ws = _empty(nbytes, dtype=torch.uint8, device=img_u8.device)
+    buf = _empty((n, bound), dtype=torch.uint8, device=img_u8.device)
+    sizes = _empty((n,), dtype=torch.int64, device=img_u8.device)
+    _lib.check(lib.cgan_jpeg_encode_u8(_ptr(img_u8), n, h, w, c, quality, sub, _ptr(buf), bound, _ptr(sizes), _ptr(ws),
+                                       nbytes, _stream()), "cgan_jpeg_encode_u8")
+    return buf, sizes
+
+
+def jpeg_coefficients(img_u8: torch.Tensor, quality: int = 90, subsampling="444") -> torch.Tensor:
+    """The encoder's transform stage alone: int16 [N, blocks * 64], the quantised coefficients ``jpeg_encode`` codes (the
+    same kernel, stopped behind the quantisation).  Per image the components Y, Cb, Cr one after the other, each its 8 x 8
+    blocks in raster order over the frame padded to whole MCUs, each block in natural order (climategan_hip.h)."""
+    n, h, w, c, quality, sub = _jpeg_args("jpeg_coefficients", img_u8, quality, subsampling)
+    v = 2 if (c == 3 and sub == 420) else 1
+    mx, my = -(-w // (8 * v)), -(-h // (8 * v))
+    blocks = mx * my * (v * v + (2 if c == 3 else 0))
+    coef = _empty((n, blocks * 64), dtype=torch.int16, device=img_u8.device)
+    _lib.check(_lib.load().cgan_jpeg_coefficients_u8(_ptr(img_u8), n, h, w, c, quality, sub, _ptr(coef), _stream()),
+               "cgan_jpeg_coefficients_u8")
+    return coef
+
+
 def smog(x: torch.Tensor, depth: NHWC, airlight: float, beta: float, alpha: float, yellow_rgb01) -> torch.Tensor:
     """Smog event (reference trainer.py:1879-1939): x NCHW fp32 in [-1, 1], depth the decoder's 1-channel NHWC map;
     returns the smogged image, NCHW fp32."""

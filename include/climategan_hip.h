@@ -659,6 +659,39 @@ int cgan_png_encode_u8_level(const uint8_t* in, int32_t n, int32_t h, int32_t w,
  * length 1.  More used symbols than 2^limit, or counts that sum above 2^32 - 1: CGAN_ERR_BAD_ARG. */
 int cgan_png_huffman_lengths(const uint32_t* counts, int32_t n, int32_t limit, uint8_t* lengths);
 
+/* JPEG files on the device.  in: uint8 [n][h][w][c], c = 1 (grey) or 3 (RGB), 1 <= w <= 4096, 1 <= h <= 65535,
+ * 1 <= n <= 65535; quality 1 .. 100; subsampling 444 or 420 (c = 1: no difference) -> out + i * out_pitch: a complete
+ * baseline JPEG file of image i, sizes[i]: its length.  The bytes of out behind sizes[i] are left as they were.
+ *   Format: SOI, APP0 (JFIF 1.01, density 1 : 1), one DQT per table (Annex K.1 / K.2 scaled by libjpeg's quality rule), SOF0
+ *   (components 1, 2, 3; luma 1x1 or 2x2), one DHT per table (Annex K.3), DRI (one MCU row), SOS, and per MCU row the
+ *   entropy-coded data padded with ones, RSTm (m = row mod 8) behind every row but the last; EOI.
+ *   Pixels: JFIF full-range BT.601 YCbCr, level shift 128, no rounding before the transform; 4:2:0 chroma is the mean of
+ *   each 2 x 2 group; the last column and row are repeated up to the MCU; orthonormal 8 x 8 DCT in fp32; coefficient / table
+ *   entry rounded to nearest, AC values clamped to +-1023.
+ * A file never exceeds cgan_jpeg_bound_bytes (22 + 63 * 26 bits per block, padded to a byte per MCU row, doubled for the
+ * stuffed 00 bytes, 2 bytes of RSTm per row, the headers, EOI); out_pitch must be at least that; the workspace (16-byte
+ * aligned) holds one staging slot per MCU row.  The bytes of a file depend on its image alone: not on the batch, not on the
+ * run.  The two size queries return 0 (and set the error text) for arguments the encoder refuses. */
+size_t cgan_jpeg_bound_bytes(int32_t h, int32_t w, int32_t c, int32_t subsampling);
+size_t cgan_jpeg_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t subsampling);
+int cgan_jpeg_encode_u8(const uint8_t* in, int32_t n, int32_t h, int32_t w, int32_t c, int32_t quality, int32_t subsampling,
+                        uint8_t* out, size_t out_pitch, int64_t* sizes, void* workspace, size_t workspace_bytes,
+                        void* stream);
+/* The encoder's transform stage alone (the same kernel, stopped behind the quantisation): the quantised coefficients of
+ * every image, n * blocks * 64 values.  Layout per image: the components Y, Cb, Cr one after the other; each its 8 x 8
+ * blocks in raster order over the frame padded to whole MCUs (mx = ceil(w / mcu), my = ceil(h / mcu) MCUs of 8 or, 4:2:0,
+ * 16 pixels: luma my * v rows of mx * v blocks with v = 2 for 4:2:0 and 1 otherwise, chroma my rows of mx blocks); each
+ * block 64 values in natural (row-major) order. */
+int cgan_jpeg_coefficients_u8(const uint8_t* in, int32_t n, int32_t h, int32_t w, int32_t c, int32_t quality,
+                              int32_t subsampling, int16_t* coef, void* stream);
+/* Host only (launch nothing, need no GPU).  cgan_jpeg_tables: the two scaled quantisation tables, natural order.
+ * cgan_jpeg_scan_host: the complete file of ONE image from coefficients in the layout above (DC in -1024 .. 1023, AC in
+ * +-1023, else CGAN_ERR_BAD_ARG), produced by the functions the kernels run (csrc/jpeg_tables.h); `quality` selects the
+ * tables the DQT segments announce.  *size: the file's length; more than cap: CGAN_ERR_BAD_ARG, *size still set. */
+int cgan_jpeg_tables(int32_t quality, uint8_t* luma, uint8_t* chroma);
+int cgan_jpeg_scan_host(const int16_t* coef, int32_t h, int32_t w, int32_t c, int32_t quality, int32_t subsampling,
+                        uint8_t* out, size_t cap, size_t* size);
+
 /* Smog event (Trainer.compute_smog, climategan/trainer.py:1879-1939, parameters shared/trainer/events.yaml:9-14):
  * irradiance = srgb2lrgb(normalize(x)) (tutils.py:534-538), depth = normalize(1 / normalize(d, 0.3, 1), 0.1, 1)
  * bilinearly resized (align_corners=True) to (h, w), transmission = exp(-beta depth),
