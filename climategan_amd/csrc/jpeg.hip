@@ -13,18 +13,20 @@
 //   jpeg_finish_kernel  one workgroup per image: the headers, the rows' offsets (exclusive scan of their sizes), EOI, the
 //                       file's length
 //   jpeg_gather_kernel  one workgroup per (MCU row, image): the row's data from its slot to its place, its RSTm behind it
+// The assembly of a file from its rows (workgroup scan, row offsets, row copy, workspace tables) is row_files.h, shared with
+// png.hip.
 //
 // No atomics on global memory and no order-dependent sums: the bytes of an image do not depend on the batch it is in or on
 // the run.
 #include "cgan_common.h"
 #include "jpeg_tables.h"
+#include "row_files.h"
 
 namespace {
 
 using jpeg_tab::Geometry;
 
-constexpr int JPEG_T = 256;                 // threads per workgroup, all three kernels
-constexpr int JPEG_MAX_W = 4096;            // the PNG encoder's limit; the segment loop itself has none
+using row_files::T;                         // threads per workgroup, all three kernels
 constexpr int JPEG_MAX_H = 65535;           // SOF0 holds 16 bits
 constexpr int SEG_PX = 256;                 // pixels of an MCU row per segment
 constexpr int SEG_BLOCKS = 96;              // blocks of a segment at most: 32 MCUs x 3 (4:4:4), 16 x 6 (4:2:0)
@@ -72,7 +74,7 @@ struct LdsBits {
 __device__ inline uint32_t bits_byte(const uint32_t* bb, uint32_t k) { return (bb[k >> 2] >> (24u - 8u * (k & 3u))) & 255u; }
 
 // One workgroup per (MCU row, image).  coef_out != nullptr: the quantised coefficients, nothing else.
-__global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __restrict__ in, size_t in_bytes, int h, int w, int c,
+__global__ __launch_bounds__(T) void jpeg_rows_kernel(const uint8_t* __restrict__ in, size_t in_bytes, int h, int w, int c,
                                                            int sub420, int quality, uint32_t* __restrict__ row_size,
                                                            uint8_t* __restrict__ staging, uint32_t slot_bytes,
                                                            int16_t* __restrict__ coef_out) {
@@ -80,8 +82,8 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
   __shared__ __attribute__((aligned(16))) unsigned char rawc[RAW_BYTES];       // the staged pixel rows, then the coefficients
   __shared__ uint32_t codes[4][256];
   __shared__ float recip[2][64];
-  __shared__ uint32_t scratch[JPEG_T];
-  __shared__ uint32_t wave_ff[JPEG_T / 64];
+  __shared__ uint32_t scratch[T];
+  __shared__ uint32_t wave_ff[T / 64];
   __shared__ int dc_carry[3];
   float* planes = reinterpret_cast<float*>(big);
   int16_t* coef = reinterpret_cast<int16_t*>(rawc);
@@ -119,7 +121,7 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
     };
     {
       const int per_row = (15 + real_w * c + 15) / 16;               // granules that can hold bytes of the row
-      for (int k = t; k < g.mcu * per_row; k += JPEG_T) {
+      for (int k = t; k < g.mcu * per_row; k += T) {
         const int r = k / per_row, gi = k % per_row;
         const uint8_t* p = row_ptr(r);
         const uint8_t* a = p - (reinterpret_cast<uintptr_t>(p) & 15u) + 16 * gi;
@@ -137,12 +139,12 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
     //      columns right of the image repeat its last column ----------------------------------------------------------
     auto pixel = [&](int r, int x) { return rawc + r * RAW_STRIDE + (reinterpret_cast<uintptr_t>(row_ptr(r)) & 15u) + (x < real_w ? x : real_w - 1) * c; };
     if (c == 1) {
-      for (int k = t; k < 8 * segw; k += JPEG_T) {
+      for (int k = t; k < 8 * segw; k += T) {
         const int r = k / segw, x = k % segw;
         planes[k] = (float)pixel(r, x)[0] - 128.f;
       }
     } else if (g.v == 1) {
-      for (int k = t; k < 8 * segw; k += JPEG_T) {
+      for (int k = t; k < 8 * segw; k += T) {
         const int r = k / segw, x = k % segw;
         const unsigned char* p = pixel(r, x);
         const float R = p[0], G = p[1], B = p[2];
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
         pl_cr[k] = 0.5f * R - 0.418688f * G - 0.081312f * B;
       }
     } else {
-      for (int k = t; k < 8 * cw; k += JPEG_T) {
+      for (int k = t; k < 8 * cw; k += T) {
         const int r = k / cw, x = k % cw;
         float cb = 0.f, cr = 0.f;
 #pragma unroll
@@ -171,7 +173,7 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
 
     // ---- DCT along the rows, in place: every plane's width is a multiple of 8, so the planes are one run of 8-value pieces -
     const int plane_floats = g.mcu * segw + (c == 3 ? 2 * 8 * cw : 0);
-    for (int k = t; k < plane_floats / 8; k += JPEG_T) {
+    for (int k = t; k < plane_floats / 8; k += T) {
       float v[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) v[i] = planes[8 * k + i];
@@ -182,7 +184,7 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
     __syncthreads();
 
     // ---- DCT along the columns and quantisation: one thread per (block, column); the blocks in scan order --------------------
-    for (int k = t; k < nb * 8; k += JPEG_T) {
+    for (int k = t; k < nb * 8; k += T) {
       const int b = k >> 3, j = k & 7;
       const int m = b / g.bpm, kb = b % g.bpm;
       const float* src;
@@ -208,7 +210,7 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
     __syncthreads();
 
     if (coef_out) {
-      for (int k = t; k < nb * 64; k += JPEG_T) {
+      for (int k = t; k < nb * 64; k += T) {
         const int b = k >> 6;
         int comp;
         const int64_t gb = jpeg_tab::coef_block(g, my, x0 / g.mcu + b / g.bpm, b % g.bpm, comp);
@@ -231,16 +233,11 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
       bits = jpeg_tab::block_bits(coef + t * COEF_STRIDE, prev_dc, dc_codes, ac_codes);
     }
     scratch[t] = bits;
-    for (int k = t; k < BB_WORDS; k += JPEG_T)                       // the planes are dead: the bit buffer takes their place
+    for (int k = t; k < BB_WORDS; k += T)                       // the planes are dead: the bit buffer takes their place
       big[k] = k == 0 ? left : 0u;
     __syncthreads();
-    for (int s = 1; s < JPEG_T; s <<= 1) {
-      const uint32_t x = t >= s ? scratch[t - s] : 0u;
-      __syncthreads();
-      scratch[t] += x;
-      __syncthreads();
-    }
-    uint32_t total_bits = carry_bits + scratch[JPEG_T - 1];
+    row_files::scan(scratch);
+    uint32_t total_bits = carry_bits + scratch[T - 1];
     if (t < nb) {
       LdsBits sink{big, carry_bits + scratch[t] - bits};
       jpeg_tab::code_block(coef + t * COEF_STRIDE, prev_dc, dc_codes, ac_codes, sink);
@@ -258,7 +255,7 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
     // ---- the whole bytes to the slot, 00 behind every FF ------------------------------------------------------------------
     const uint32_t nbytes = total_bits >> 3;
     uint32_t ff_before = 0;
-    for (uint32_t k0 = 0; k0 < nbytes; k0 += JPEG_T) {
+    for (uint32_t k0 = 0; k0 < nbytes; k0 += T) {
       const uint32_t k = k0 + t;
       const uint32_t byte = k < nbytes ? bits_byte(big, k) : 0u;
       const bool ff = byte == 0xFFu;
@@ -267,7 +264,7 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
       if (lane == 0) wave_ff[wave] = (uint32_t)__popcll(mask);
       __syncthreads();
       uint32_t pre = ff_before + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)), all = 0;
-      for (int u = 0; u < JPEG_T / 64; ++u) {
+      for (int u = 0; u < T / 64; ++u) {
         if (u < wave) pre += wave_ff[u];
         all += wave_ff[u];
       }
@@ -288,56 +285,35 @@ __global__ __launch_bounds__(JPEG_T) void jpeg_rows_kernel(const uint8_t* __rest
 }
 
 // one workgroup per image
-__global__ __launch_bounds__(JPEG_T) void jpeg_finish_kernel(int h, int w, int c, int sub420, int quality, int rows,
+__global__ __launch_bounds__(T) void jpeg_finish_kernel(int h, int w, int c, int sub420, int quality, int rows,
                                                              const uint32_t* __restrict__ row_size,
                                                              uint32_t* __restrict__ row_off, uint8_t* __restrict__ out,
                                                              size_t out_pitch, long long* __restrict__ sizes) {
-  __shared__ uint32_t scratch[JPEG_T];
-  const int t = threadIdx.x;
+  __shared__ uint32_t scratch[T];
   const size_t base = (size_t)blockIdx.x * rows;
-  // offsets of the rows' data: exclusive scan of their sizes (an RSTm, 2 bytes, behind each but the last), JPEG_T at a time
-  uint32_t running = jpeg_tab::header_bytes(c);
-  for (int r0 = 0; r0 < rows; r0 += JPEG_T) {
-    const int r = r0 + t;
-    const uint32_t v = r < rows ? row_size[base + r] + (r + 1 < rows ? 2u : 0u) : 0u;
-    scratch[t] = v;
-    __syncthreads();
-    for (int s = 1; s < JPEG_T; s <<= 1) {
-      const uint32_t x = t >= s ? scratch[t - s] : 0u;
-      __syncthreads();
-      scratch[t] += x;
-      __syncthreads();
-    }
-    if (r < rows) row_off[base + r] = running + scratch[t] - v;
-    running += scratch[JPEG_T - 1];
-    __syncthreads();
-  }
-  if (t != 0) return;
+  // the rows' data follows the headers, an RSTm (2 bytes) behind each row but the last
+  const uint32_t running = row_files::row_offsets(scratch, row_size + base, row_off + base, rows, jpeg_tab::header_bytes(c), 2u);
+  if (threadIdx.x != 0) return;
   uint8_t* f = out + (size_t)blockIdx.x * out_pitch;
   jpeg_tab::write_headers(f, h, w, c, sub420, quality);
   f[running] = 0xFF, f[running + 1u] = 0xD9;
   sizes[blockIdx.x] = (long long)running + 2;
 }
 
-// one workgroup per (MCU row, image): the data starts at any byte offset of the file, so it moves byte by byte
-__global__ __launch_bounds__(JPEG_T) void jpeg_gather_kernel(int rows, const uint32_t* __restrict__ row_size,
+// one workgroup per (MCU row, image): the row's data, its RSTm behind it
+__global__ __launch_bounds__(T) void jpeg_gather_kernel(int rows, const uint32_t* __restrict__ row_size,
                                                              const uint32_t* __restrict__ row_off,
                                                              const uint8_t* __restrict__ staging, uint32_t slot_bytes,
                                                              uint8_t* __restrict__ out, size_t out_pitch) {
   const int r = blockIdx.x;
   const size_t idx = (size_t)blockIdx.y * rows + r;
-  const uint32_t size = row_size[idx];
-  const uint8_t* src = staging + idx * slot_bytes;
-  uint8_t* dst = out + (size_t)blockIdx.y * out_pitch + row_off[idx];
-  for (uint32_t k = threadIdx.x; k < size; k += JPEG_T) dst[k] = src[k];
-  if (threadIdx.x == 0 && r + 1 < rows) dst[size] = 0xFF, dst[size + 1u] = (uint8_t)(0xD0 + (r & 7));
+  uint8_t* end = row_files::copy_row(staging + idx * slot_bytes, 0u, row_size[idx],
+                                     out + (size_t)blockIdx.y * out_pitch + row_off[idx]);
+  if (threadIdx.x == 0 && r + 1 < rows) end[0] = 0xFF, end[1] = (uint8_t)(0xD0 + (r & 7));
 }
 
 bool jpeg_args_ok(const char* what, int64_t n, int32_t h, int32_t w, int32_t c, int32_t quality, int32_t subsampling) {
-  if (c != 1 && c != 3) {
-    cgan_set_error("%s: c = %d: 8-bit grey (1) or RGB (3) only", what, c);
-    return false;
-  }
+  if (!row_files::channels_ok(what, c)) return false;
   if (subsampling != 444 && subsampling != 420) {
     cgan_set_error("%s: subsampling = %d: 444 or 420 only", what, subsampling);
     return false;
@@ -346,24 +322,17 @@ bool jpeg_args_ok(const char* what, int64_t n, int32_t h, int32_t w, int32_t c, 
     cgan_set_error("%s: quality = %d: 1 to 100 only", what, quality);
     return false;
   }
-  if (w < 1 || w > JPEG_MAX_W || h < 1 || h > JPEG_MAX_H) {
-    cgan_set_error("%s: h = %d, w = %d: 1 to %d rows of 1 to %d pixels only", what, h, w, JPEG_MAX_H, JPEG_MAX_W);
+  if (w < 1 || w > row_files::MAX_W || h < 1 || h > JPEG_MAX_H) {
+    cgan_set_error("%s: h = %d, w = %d: 1 to %d rows of 1 to %d pixels only", what, h, w, JPEG_MAX_H, row_files::MAX_W);
     return false;
   }
   const Geometry g = jpeg_tab::geometry(h, w, c, subsampling == 420);
-  if (n < 1 || n > 65535 || n * (int64_t)g.mcus_y > 0x7fffffffll) {
+  if (!row_files::grid_ok(n, g.mcus_y)) {
     cgan_set_error("%s: n = %lld: 1 <= n <= 65535 expected", what, (long long)n);
     return false;
   }
-  if (jpeg_tab::file_max_bytes(g) > 0x7fffffffull) {
-    cgan_set_error("%s: a %d x %d x %d image may need %llu bytes, more than the 2^31 - 1 one file may have", what, h, w, c,
-                   (unsigned long long)jpeg_tab::file_max_bytes(g));
-    return false;
-  }
-  return true;
+  return row_files::file_fits(what, h, w, c, jpeg_tab::file_max_bytes(g));
 }
-
-size_t jpeg_table_bytes(int64_t rows) { return (size_t)((rows * 4 + 15) / 16 * 16); }
 
 }  // namespace
 
@@ -381,7 +350,7 @@ extern "C" size_t cgan_jpeg_workspace_bytes(int32_t n, int32_t h, int32_t w, int
   if (!jpeg_args_ok("cgan_jpeg_workspace_bytes", n, h, w, c, 50, subsampling)) return 0;
   const Geometry g = jpeg_tab::geometry(h, w, c, subsampling == 420);
   const int64_t rows = (int64_t)n * g.mcus_y;
-  return 2 * jpeg_table_bytes(rows) + (size_t)rows * jpeg_slot_bytes(g);
+  return 2 * row_files::table_bytes(rows) + (size_t)rows * jpeg_slot_bytes(g);
 }
 
 extern "C" int cgan_jpeg_encode_u8(const uint8_t* in, int32_t n, int32_t h, int32_t w, int32_t c, int32_t quality,
@@ -389,30 +358,24 @@ extern "C" int cgan_jpeg_encode_u8(const uint8_t* in, int32_t n, int32_t h, int3
                                    size_t workspace_bytes, void* stream) {
   CGAN_REQUIRE(in && out && sizes && workspace, "cgan_jpeg_encode_u8: null pointer");
   if (!jpeg_args_ok("cgan_jpeg_encode_u8", n, h, w, c, quality, subsampling)) return CGAN_ERR_BAD_ARG;
-  const size_t bound = cgan_jpeg_bound_bytes(h, w, c, subsampling);
-  CGAN_REQUIRE(out_pitch >= bound, "cgan_jpeg_encode_u8: out_pitch %zu is below the bound %zu", out_pitch, bound);
-  const size_t need = cgan_jpeg_workspace_bytes(n, h, w, c, subsampling);
-  if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u)) {
-    cgan_set_error("cgan_jpeg_encode_u8: workspace of %zu bytes (16-byte aligned) expected, got %zu at %p", need,
-                   workspace_bytes, workspace);
-    return CGAN_ERR_WORKSPACE;
-  }
+  if (const int rc = row_files::buffers_ok("cgan_jpeg_encode_u8", out_pitch, cgan_jpeg_bound_bytes(h, w, c, subsampling),
+                                          workspace, workspace_bytes, cgan_jpeg_workspace_bytes(n, h, w, c, subsampling)))
+    return rc;
   const int sub420 = subsampling == 420;
   const Geometry g = jpeg_tab::geometry(h, w, c, sub420);
-  const size_t tb = jpeg_table_bytes((int64_t)n * g.mcus_y);
-  uint8_t* ws = static_cast<uint8_t*>(workspace);
-  uint32_t* row_size = reinterpret_cast<uint32_t*>(ws);
-  uint32_t* row_off = reinterpret_cast<uint32_t*>(ws + tb);
-  uint8_t* staging = ws + 2 * tb;
+  const int64_t all_rows = (int64_t)n * g.mcus_y;
+  uint32_t* row_size = row_files::table(workspace, all_rows, 0);
+  uint32_t* row_off = row_files::table(workspace, all_rows, 1);
+  uint8_t* staging = reinterpret_cast<uint8_t*>(row_files::table(workspace, all_rows, 2));
   const uint32_t slot = jpeg_slot_bytes(g);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(jpeg_rows_kernel, dim3(g.mcus_y, n), dim3(JPEG_T), 0, s, in, (size_t)n * h * w * c, h, w, c, sub420,
+  hipLaunchKernelGGL(jpeg_rows_kernel, dim3(g.mcus_y, n), dim3(T), 0, s, in, (size_t)n * h * w * c, h, w, c, sub420,
                      quality, row_size, staging, slot, static_cast<int16_t*>(nullptr));
   CGAN_CHECK_LAUNCH("cgan_jpeg_encode_u8 (rows)");
-  hipLaunchKernelGGL(jpeg_finish_kernel, dim3(n), dim3(JPEG_T), 0, s, h, w, c, sub420, quality, g.mcus_y, row_size, row_off,
+  hipLaunchKernelGGL(jpeg_finish_kernel, dim3(n), dim3(T), 0, s, h, w, c, sub420, quality, g.mcus_y, row_size, row_off,
                      out, out_pitch, reinterpret_cast<long long*>(sizes));
   CGAN_CHECK_LAUNCH("cgan_jpeg_encode_u8 (finish)");
-  hipLaunchKernelGGL(jpeg_gather_kernel, dim3(g.mcus_y, n), dim3(JPEG_T), 0, s, g.mcus_y, row_size, row_off, staging, slot,
+  hipLaunchKernelGGL(jpeg_gather_kernel, dim3(g.mcus_y, n), dim3(T), 0, s, g.mcus_y, row_size, row_off, staging, slot,
                      out, out_pitch);
   CGAN_CHECK_LAUNCH("cgan_jpeg_encode_u8 (gather)");
   return CGAN_OK;
@@ -424,7 +387,7 @@ extern "C" int cgan_jpeg_coefficients_u8(const uint8_t* in, int32_t n, int32_t h
   if (!jpeg_args_ok("cgan_jpeg_coefficients_u8", n, h, w, c, quality, subsampling)) return CGAN_ERR_BAD_ARG;
   const int sub420 = subsampling == 420;
   const Geometry g = jpeg_tab::geometry(h, w, c, sub420);
-  hipLaunchKernelGGL(jpeg_rows_kernel, dim3(g.mcus_y, n), dim3(JPEG_T), 0, static_cast<hipStream_t>(stream), in,
+  hipLaunchKernelGGL(jpeg_rows_kernel, dim3(g.mcus_y, n), dim3(T), 0, static_cast<hipStream_t>(stream), in,
                      (size_t)n * h * w * c, h, w, c, sub420, quality, static_cast<uint32_t*>(nullptr),
                      static_cast<uint8_t*>(nullptr), 0u, coef);
   CGAN_CHECK_LAUNCH("cgan_jpeg_coefficients_u8");

@@ -13,18 +13,20 @@
 //   png_finish_kernel  one workgroup per image: signature, IHDR, row offsets (exclusive scan of the chunk sizes), the
 //                      combined Adler-32, closing IDAT, IEND, the file's length
 //   png_gather_kernel  one workgroup per (row, image): the row's chunk from its staging slot to its place in the file
+// The assembly of a file from its rows (workgroup scan, row offsets, row copy, workspace tables) is row_files.h, shared with
+// jpeg.hip.
 //
 // No atomics on global memory and fixed-order reductions: the bytes of an image do not depend on the batch it is in or on
 // the run.
 #include "cgan_common.h"
 #include "png_huffman.h"
+#include "row_files.h"
 
 #include <vector>
 
 namespace {
 
-constexpr int PNG_T = 256;                  // threads per workgroup, all three kernels
-constexpr int PNG_MAX_W = 4096;             // widest row: 4096 pixels (12 288 filtered bytes as RGB)
+using row_files::T;                         // threads per workgroup, all three kernels
 constexpr uint32_t ADLER_MOD = 65521u;
 constexpr uint32_t CRC_POLY = 0xEDB88320u;
 constexpr uint32_t PNG_FIXED_BYTES = 8 + 25 + 2 + 18 + 12;   // signature, IHDR, zlib header, closing IDAT, IEND
@@ -83,7 +85,7 @@ __host__ __device__ inline PngLds png_lds(uint32_t m) {
   o.len = o.d + mb;
   o.flags = o.len + mb;
   o.scratch = o.flags + mb;
-  o.total = o.scratch + 5u * PNG_T * 4u;
+  o.total = o.scratch + 5u * T * 4u;
   return o;
 }
 
@@ -133,26 +135,6 @@ __device__ inline uint32_t literal_token(uint32_t b, uint32_t& nbits) {
   nbits = 9;
   return bit_rev(0x190u + (b - 144u), 9);
 }
-// l = length - 3 (0..255), dist_c: distance 3 instead of 1
-__device__ inline uint32_t match_token(uint32_t l, bool dist3, uint32_t& nbits) {
-  uint32_t code, eb = 0, ev = 0;
-  if (l < 8u) {
-    code = 257u + l;
-  } else if (l == 255u) {
-    code = 285u;
-  } else {
-    eb = (31u - (uint32_t)__clz(l)) - 2u;
-    code = 261u + 4u * eb + ((l >> eb) & 3u);
-    ev = l & ((1u << eb) - 1u);
-  }
-  const uint32_t hb = code < 280u ? 7u : 8u;
-  const uint32_t huff = code < 280u ? code - 256u : 0xC0u + (code - 280u);
-  // distance codes 0 (distance 1) and 2 (distance 3): 5 bits, no extra bits; 00010 reversed = 01000
-  const uint32_t dist = dist3 ? 8u : 0u;
-  nbits = hb + eb + 5u;
-  return bit_rev(huff, hb) | (ev << hb) | (dist << (hb + eb));
-}
-// ---- level 2: the same tokens under another code ------------------------------------------------------------------------
 // length symbol 257..285 of l = length - 3, its extra bits and their value
 __device__ inline uint32_t length_symbol(uint32_t l, uint32_t& eb, uint32_t& ev) {
   eb = 0, ev = 0;
@@ -162,6 +144,18 @@ __device__ inline uint32_t length_symbol(uint32_t l, uint32_t& eb, uint32_t& ev)
   ev = l & ((1u << eb) - 1u);
   return 261u + 4u * eb + ((l >> eb) & 3u);
 }
+// l = length - 3 (0..255), dist_c: distance 3 instead of 1
+__device__ inline uint32_t match_token(uint32_t l, bool dist3, uint32_t& nbits) {
+  uint32_t eb, ev;
+  const uint32_t code = length_symbol(l, eb, ev);
+  const uint32_t hb = code < 280u ? 7u : 8u;
+  const uint32_t huff = code < 280u ? code - 256u : 0xC0u + (code - 280u);
+  // distance codes 0 (distance 1) and 2 (distance 3): 5 bits, no extra bits; 00010 reversed = 01000
+  const uint32_t dist = dist3 ? 8u : 0u;
+  nbits = hb + eb + 5u;
+  return bit_rev(huff, hb) | (ev << hb) | (dist << (hb + eb));
+}
+// ---- level 2: the same tokens under another code ------------------------------------------------------------------------
 __device__ inline uint32_t symbol_extra_bits(uint32_t s) { return (s < 265u || s == 285u) ? 0u : (s - 261u) >> 2; }
 __device__ inline uint32_t fixed_code_bits(uint32_t s) { return s < 144u ? 8u : (s < 256u ? 9u : (s < 280u ? 7u : 8u)); }
 // The distance code is declared complete and never built: lengths {1, 1} (c = 1) or {1, 0, 1} (c = 3), so distance 1 (code
@@ -181,12 +175,12 @@ __device__ inline void emit_bits(uint32_t* bb, uint32_t pos, uint32_t v, uint32_
   if (sh + nbits > 32u) atomicOr(&bb[wi + 1u], v >> (32u - sh));
 }
 
-// sum over the workgroup, returned to every thread; s: PNG_T words of LDS
+// sum over the workgroup, returned to every thread; s: T words of LDS
 __device__ inline uint32_t block_sum(uint32_t* s, uint32_t v) {
   const int t = threadIdx.x;
   s[t] = v;
   __syncthreads();
-  for (int k = PNG_T / 2; k > 0; k >>= 1) {
+  for (int k = T / 2; k > 0; k >>= 1) {
     if (t < k) s[t] += s[t + k];
     __syncthreads();
   }
@@ -214,7 +208,7 @@ __device__ inline uint32_t png_filter(int f, uint32_t x, uint32_t a, uint32_t b,
 // the fixed, dynamic and stored coding (first on ties), PNG_H_BYTES more LDS behind PngLds::total.
 enum : uint32_t { PNG_FIXED = 1, PNG_DYNAMIC = 2, PNG_STORED = 0 };         // = BTYPE
 template <int LEVEL>
-__global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restrict__ in, int h, int row_len, int c,
+__global__ __launch_bounds__(T) void png_rows_kernel(const uint8_t* __restrict__ in, int h, int row_len, int c,
                                                          uint32_t* __restrict__ row_size, uint32_t* __restrict__ row_s1,
                                                          uint32_t* __restrict__ row_s2, uint8_t* __restrict__ staging,
                                                          uint32_t slot_bytes) {
@@ -239,12 +233,12 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
   if ((L & 15u) == 0 && (reinterpret_cast<uintptr_t>(in) & 15u) == 0) {
     const uint4* s4 = reinterpret_cast<const uint4*>(src);
     const uint4* p4 = reinterpret_cast<const uint4*>(src - L);
-    for (uint32_t k = t; k < L / 16u; k += PNG_T) {
+    for (uint32_t k = t; k < L / 16u; k += T) {
       reinterpret_cast<uint4*>(cur)[k] = s4[k];
       reinterpret_cast<uint4*>(prev)[k] = r > 0 ? p4[k] : make_uint4(0, 0, 0, 0);
     }
   } else {
-    for (uint32_t k = t; k < L; k += PNG_T) {
+    for (uint32_t k = t; k < L; k += T) {
       cur[k] = src[k];
       prev[k] = r > 0 ? src[(ptrdiff_t)k - (ptrdiff_t)L] : (uint8_t)0;
     }
@@ -253,7 +247,7 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
 
   // ---- filter choice: the smallest sum of |filtered byte as int8| over None, Sub, Up, Average, Paeth ---------------------
   uint32_t cost[5] = {0, 0, 0, 0, 0};
-  for (uint32_t i = t; i < L; i += PNG_T) {
+  for (uint32_t i = t; i < L; i += T) {
     const uint32_t x = cur[i], b = prev[i];
     const uint32_t a = i >= (uint32_t)c ? cur[i - c] : 0u, cc = i >= (uint32_t)c ? prev[i - c] : 0u;
 #pragma unroll
@@ -273,7 +267,7 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
   // ---- filtered bytes d[0 .. m) (d[0] = the filter type) and the row's Adler-32 part:
   //      s1 = sum d[k], s2 = sum (m - k) d[k]  (what the row adds to A, and to B beyond m * A) ------------------------------
   uint32_t s1 = 0, s2 = 0;                 // per thread at most 49 terms of at most 255 * 12 289: no overflow
-  for (uint32_t i = t; i < L; i += PNG_T) {
+  for (uint32_t i = t; i < L; i += T) {
     const uint32_t x = cur[i], b = prev[i];
     const uint32_t a = i >= (uint32_t)c ? cur[i - c] : 0u, cc = i >= (uint32_t)c ? prev[i - c] : 0u;
     const uint32_t v = png_filter(best, x, a, b, cc);
@@ -296,11 +290,11 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
   // ---- greedy parse: at i take the longer of the runs d[i..] == d[i-1..] and d[i..] == d[i-c..] (3..258 bytes, inside the
   //      row), else a literal.  Each thread owns a contiguous piece; the run lengths come from a backward walk that starts
   //      from the first mismatch in the pieces to the right. ------------------------------------------------------------
-  const uint32_t piece = (m + PNG_T - 1u) / PNG_T;
+  const uint32_t piece = (m + T - 1u) / T;
   const uint32_t lo = (uint32_t)t * piece < m ? (uint32_t)t * piece : m;
   const uint32_t hi = lo + piece < m ? lo + piece : m;
   uint32_t* ff1 = scratch;                  // first position of the piece where the distance-1 / distance-c run breaks
-  uint32_t* ffc = scratch + PNG_T;
+  uint32_t* ffc = scratch + T;
   {
     uint32_t f1 = m, fc = m;
     for (uint32_t i = lo; i < hi; ++i) {
@@ -315,8 +309,8 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
   __syncthreads();
   {
     uint32_t end1 = m, endc = m;            // first break at or after hi (m: the end of the row)
-    for (int u = t + 1; u < PNG_T && end1 == m; ++u) end1 = ff1[u];
-    for (int u = t + 1; u < PNG_T && endc == m; ++u) endc = ffc[u];
+    for (int u = t + 1; u < T && end1 == m; ++u) end1 = ff1[u];
+    for (int u = t + 1; u < T && endc == m; ++u) endc = ffc[u];
     for (uint32_t i = hi; i-- > lo;) {
       if (!(i >= 1u && d[i] == d[i - 1u])) end1 = i;
       if (!(i >= (uint32_t)c && d[i] == d[i - c])) endc = i;
@@ -347,7 +341,7 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
     uint16_t* a = j0;
     uint16_t* b = j1;
     for (uint32_t span = 1; span < m; span <<= 1) {
-      for (uint32_t i = t; i <= m; i += PNG_T) {
+      for (uint32_t i = t; i <= m; i += T) {
         const uint32_t j = a[i];
         if (flags[i] & 1u) flags[j] |= 1u;
         b[i] = a[j];
@@ -365,8 +359,8 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
     PNG_HUFFMAN_LDS(smem + o.total);
     uint32_t* sorted = reinterpret_cast<uint32_t*>(hs + PNG_H_SORTED);
     uint16_t* order = codes;
-    for (uint32_t k = t; k < PNG_SYMS; k += PNG_T) hist[k] = 0;
-    for (uint32_t k = t; k < 320u; k += PNG_T) lens[k] = 0;
+    for (uint32_t k = t; k < PNG_SYMS; k += T) hist[k] = 0;
+    for (uint32_t k = t; k < 320u; k += T) lens[k] = 0;
     __syncthreads();
     for (uint32_t i = lo; i < hi; ++i) {
       const uint32_t f = flags[i];
@@ -378,7 +372,7 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
     __syncthreads();
     // used symbols in ascending order of (count, symbol): every symbol counts the ones before it
     uint32_t used = 0;
-    for (uint32_t s = t; s < (uint32_t)png_huff::NUM_LITLEN; s += PNG_T) {
+    for (uint32_t s = t; s < (uint32_t)png_huff::NUM_LITLEN; s += T) {
       const uint32_t cnt = hist[s];
       uint32_t rank = 0;
       used = 0;
@@ -415,7 +409,7 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
     }
     __syncthreads();
     uint32_t fb = 0, db = 0;                               // bits of all tokens and the end of block under either code
-    for (uint32_t s = t; s < (uint32_t)png_huff::NUM_LITLEN; s += PNG_T) {
+    for (uint32_t s = t; s < (uint32_t)png_huff::NUM_LITLEN; s += T) {
       const uint32_t cnt = hist[s], x = symbol_extra_bits(s);
       fb += cnt * (fixed_code_bits(s) + x + (s > 256u ? 5u : 0u));
       db += cnt * (lens[s] + x + (s > 256u ? 1u : 0u));
@@ -432,34 +426,32 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
     dyn_bits = db;
   }
 
+  // the token that starts at i (f = flags[i]) under the row's code, fixed or dynamic -> its value, nb: its bits
+  auto token = [&](uint32_t i, uint32_t f, uint32_t& nb) -> uint32_t {
+    if constexpr (LEVEL == 2) {
+      if (mode == PNG_DYNAMIC) {
+        PNG_HUFFMAN_LDS(smem + o.total);
+        if (f & 2u) return dynamic_match_token(lenm3[i], (f & 4u) != 0, codes, lens, nb);
+        nb = lens[d[i]];
+        return codes[d[i]];
+      }
+    }
+    return (f & 2u) ? match_token(lenm3[i], (f & 4u) != 0, nb) : literal_token(d[i], nb);
+  };
+
   // ---- bit offsets of the tokens: sum per piece, exclusive scan over the pieces ------------------------------------------
   uint32_t bits = 0;
   for (uint32_t i = lo; i < hi; ++i) {
     const uint32_t f = flags[i];
     if (!(f & 1u)) continue;
     uint32_t nb;
-    if constexpr (LEVEL == 2) {
-      PNG_HUFFMAN_LDS(smem + o.total);
-      if (mode == PNG_DYNAMIC) {
-        if (f & 2u) dynamic_match_token(lenm3[i], (f & 4u) != 0, codes, lens, nb);
-        else nb = lens[d[i]];
-        bits += nb;
-        continue;
-      }
-    }
-    if (f & 2u) match_token(lenm3[i], (f & 4u) != 0, nb);
-    else literal_token(d[i], nb);
+    token(i, f, nb);
     bits += nb;
   }
   scratch[t] = bits;
   __syncthreads();
-  for (int s = 1; s < PNG_T; s <<= 1) {
-    const uint32_t x = t >= s ? scratch[t - s] : 0u;
-    __syncthreads();
-    scratch[t] += x;
-    __syncthreads();
-  }
-  const uint32_t token_bits = scratch[PNG_T - 1];
+  row_files::scan(scratch);
+  const uint32_t token_bits = scratch[T - 1];
   uint32_t pos = 3u + scratch[t] - bits;
   // block: BFINAL 0, BTYPE 01 | tokens | end of block (7 zero bits) | stored block: BFINAL 0, BTYPE 00, padding, 00 00 FF FF
   uint32_t n = (3u + token_bits + 7u + 3u + 7u) / 8u + 4u;             // bytes of this row's deflate data
@@ -469,13 +461,13 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
     if (mode == PNG_DYNAMIC) pos += cl->header_bits;
   }
   const uint32_t bb_words = png_round_up(png_row_data_max(m) + 8u, 16u) / 4u;
-  for (uint32_t k = t; k < bb_words; k += PNG_T) bb[k] = 0;            // j0 / j1 are dead: the bit buffer takes their place
+  for (uint32_t k = t; k < bb_words; k += T) bb[k] = 0;            // j0 / j1 are dead: the bit buffer takes their place
   __syncthreads();
   if constexpr (LEVEL == 2) {
     PNG_HUFFMAN_LDS(smem + o.total);
     if (mode == PNG_STORED) {                // 00 | LEN, NLEN | the filtered bytes | 00 | 00 00 FF FF, all with byte stores
       uint8_t* b8 = reinterpret_cast<uint8_t*>(bb);
-      for (uint32_t k = t; k < m; k += PNG_T) b8[5u + k] = d[k];
+      for (uint32_t k = t; k < m; k += T) b8[5u + k] = d[k];
       if (t == 0) {
         b8[1] = (uint8_t)m, b8[2] = (uint8_t)(m >> 8);
         b8[3] = (uint8_t)~m, b8[4] = (uint8_t)(~m >> 8);
@@ -503,22 +495,11 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
     emit_bits(bb, 0, 2u, 3);
     emit_bits(bb, (n - 2u) * 8u, 0xFFFFu, 16);
   }
-  for (uint32_t i = lo; i < hi; ++i) {
+  for (uint32_t i = lo; i < hi && mode != PNG_STORED; ++i) {
     const uint32_t f = flags[i];
     if (!(f & 1u)) continue;
     uint32_t nb;
-    if constexpr (LEVEL == 2) {
-      PNG_HUFFMAN_LDS(smem + o.total);
-      if (mode == PNG_STORED) break;
-      if (mode == PNG_DYNAMIC) {
-        const uint32_t v = (f & 2u) ? dynamic_match_token(lenm3[i], (f & 4u) != 0, codes, lens, nb) : (uint32_t)codes[d[i]];
-        if (!(f & 2u)) nb = lens[d[i]];
-        emit_bits(bb, pos, v, nb);
-        pos += nb;
-        continue;
-      }
-    }
-    const uint32_t v = (f & 2u) ? match_token(lenm3[i], (f & 4u) != 0, nb) : literal_token(d[i], nb);
+    const uint32_t v = token(i, f, nb);
     emit_bits(bb, pos, v, nb);
     pos += nb;
   }
@@ -529,14 +510,14 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
   //      half is multiplied by x^(8 * bytes of the right half) ---------------------------------------------------------------
   const uint8_t* bytes = reinterpret_cast<const uint8_t*>(bb);
   {
-    const uint32_t k = (n + PNG_T - 1u) / PNG_T;
-    const int end = (int)n - (PNG_T - 1 - t) * (int)k;
+    const uint32_t k = (n + T - 1u) / T;
+    const int end = (int)n - (T - 1 - t) * (int)k;
     const int begin = end - (int)k;
     uint32_t crc = 0;
     for (int i = begin > 0 ? begin : 0; i < end; ++i) crc = crc_byte(crc, bytes[i]);
     scratch[t] = crc;
     uint32_t xp = gf_pow_x8(k);
-    for (int s = 1; s < PNG_T; s <<= 1) {
+    for (int s = 1; s < T; s <<= 1) {
       __syncthreads();
       if ((t & (2 * s - 1)) == 0) scratch[t] = gf_mul(scratch[t], xp) ^ scratch[t + s];
       xp = gf_mul(xp, xp);
@@ -558,40 +539,25 @@ __global__ __launch_bounds__(PNG_T) void png_rows_kernel(const uint8_t* __restri
   }
   __syncthreads();
   uint32_t* dst = reinterpret_cast<uint32_t*>(slot + 16u);
-  for (uint32_t k = t; k < (n + 4u + 3u) / 4u; k += PNG_T) dst[k] = bb[k];
+  for (uint32_t k = t; k < (n + 4u + 3u) / 4u; k += T) dst[k] = bb[k];
 }
 
 // one workgroup per image
-__global__ __launch_bounds__(PNG_T) void png_finish_kernel(int h, int w, int c, const uint32_t* __restrict__ row_size,
+__global__ __launch_bounds__(T) void png_finish_kernel(int h, int w, int c, const uint32_t* __restrict__ row_size,
                                                            const uint32_t* __restrict__ row_s1,
                                                            const uint32_t* __restrict__ row_s2, uint32_t* __restrict__ row_off,
                                                            uint8_t* __restrict__ out, size_t out_pitch,
                                                            long long* __restrict__ sizes) {
-  __shared__ uint32_t scratch[PNG_T];
+  __shared__ uint32_t scratch[T];
   const int t = threadIdx.x;
   const size_t base = (size_t)blockIdx.x * h;
   const uint32_t m = (uint32_t)w * (uint32_t)c + 1u;
-  // offsets of the rows' chunks: exclusive scan of their sizes, PNG_T rows at a time
-  uint32_t running = 8u + 25u;
-  for (int r0 = 0; r0 < h; r0 += PNG_T) {
-    const int r = r0 + t;
-    const uint32_t v = r < h ? row_size[base + r] : 0u;
-    scratch[t] = v;
-    __syncthreads();
-    for (int s = 1; s < PNG_T; s <<= 1) {
-      const uint32_t x = t >= s ? scratch[t - s] : 0u;
-      __syncthreads();
-      scratch[t] += x;
-      __syncthreads();
-    }
-    if (r < h) row_off[base + r] = running + scratch[t] - v;
-    running += scratch[PNG_T - 1];
-    __syncthreads();
-  }
+  // the rows' chunks follow the signature and IHDR, one behind the other
+  const uint32_t running = row_files::row_offsets(scratch, row_size + base, row_off + base, h, 8u + 25u, 0u);
   // Adler-32 of all filtered rows from the rows' parts.  Row i turns (A, B) into (A + s1_i, B + m A + s2_i); from (1, 0):
   //   A = 1 + sum s1_i,   B = m h + m sum s1_i (h - 1 - i) + sum s2_i        (mod 65521)
   uint32_t a_part = 0, b1_part = 0, b2_part = 0;
-  for (int r = t; r < h; r += PNG_T) {
+  for (int r = t; r < h; r += T) {
     const uint32_t s1 = row_s1[base + r];
     a_part = (a_part + s1) % ADLER_MOD;
     b1_part = (b1_part + s1 * ((uint32_t)(h - 1 - r) % ADLER_MOD) % ADLER_MOD) % ADLER_MOD;
@@ -633,42 +599,29 @@ __global__ __launch_bounds__(PNG_T) void png_finish_kernel(int h, int w, int c, 
   sizes[blockIdx.x] = (long long)running + 18 + 12;
 }
 
-// one workgroup per (row, image): the chunk starts at any byte offset of the file, so it moves byte by byte
-__global__ __launch_bounds__(PNG_T) void png_gather_kernel(int h, const uint32_t* __restrict__ row_size,
+// one workgroup per (row, image): the chunk, from its right-aligned header on
+__global__ __launch_bounds__(T) void png_gather_kernel(int h, const uint32_t* __restrict__ row_size,
                                                            const uint32_t* __restrict__ row_off,
                                                            const uint8_t* __restrict__ staging, uint32_t slot_bytes,
                                                            uint8_t* __restrict__ out, size_t out_pitch) {
   const int r = blockIdx.x;
   const size_t idx = (size_t)blockIdx.y * h + r;
-  const uint32_t size = row_size[idx];
-  const uint8_t* src = staging + idx * slot_bytes + (r == 0 ? 6u : 8u);
-  uint8_t* dst = out + (size_t)blockIdx.y * out_pitch + row_off[idx];
-  for (uint32_t k = threadIdx.x; k < size; k += PNG_T) dst[k] = src[k];
+  row_files::copy_row(staging + idx * slot_bytes, r == 0 ? 6u : 8u, row_size[idx],
+                      out + (size_t)blockIdx.y * out_pitch + row_off[idx]);
 }
 
 bool png_shape_ok(const char* what, int64_t n, int32_t h, int32_t w, int32_t c) {
-  if (c != 1 && c != 3) {
-    cgan_set_error("%s: c = %d: 8-bit grey (1) or RGB (3) only", what, c);
+  if (!row_files::channels_ok(what, c)) return false;
+  if (w < 1 || w > row_files::MAX_W) {
+    cgan_set_error("%s: w = %d: rows of 1 to %d pixels only", what, w, row_files::MAX_W);
     return false;
   }
-  if (w < 1 || w > PNG_MAX_W) {
-    cgan_set_error("%s: w = %d: rows of 1 to %d pixels only", what, w, PNG_MAX_W);
-    return false;
-  }
-  if (h < 1 || n < 1 || n > 65535 || n * (int64_t)h > 0x7fffffffll) {
+  if (!row_files::grid_ok(n, h)) {
     cgan_set_error("%s: n = %lld, h = %d: 1 <= n <= 65535, h >= 1 and n * h < 2^31 expected", what, (long long)n, h);
     return false;
   }
-  const uint64_t bound = PNG_FIXED_BYTES + (uint64_t)h * (12u + png_row_data_max((uint32_t)w * c + 1u));
-  if (bound > 0x7fffffffull) {
-    cgan_set_error("%s: a %d x %d x %d image may need %llu bytes, more than the 2^31 - 1 one file may have", what, h, w, c,
-                   (unsigned long long)bound);
-    return false;
-  }
-  return true;
+  return row_files::file_fits(what, h, w, c, PNG_FIXED_BYTES + (uint64_t)h * (12u + png_row_data_max((uint32_t)w * c + 1u)));
 }
-
-size_t png_table_bytes(int64_t rows) { return (size_t)((rows * 4 + 15) / 16 * 16); }
 
 }  // namespace
 
@@ -680,7 +633,7 @@ extern "C" size_t cgan_png_bound_bytes(int32_t h, int32_t w, int32_t c) {
 extern "C" size_t cgan_png_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c) {
   if (!png_shape_ok("cgan_png_workspace_bytes", n, h, w, c)) return 0;
   const int64_t rows = (int64_t)n * h;
-  return 4 * png_table_bytes(rows) + (size_t)rows * png_slot_bytes((uint32_t)w * c + 1u);
+  return 4 * row_files::table_bytes(rows) + (size_t)rows * png_slot_bytes((uint32_t)w * c + 1u);
 }
 
 extern "C" int cgan_png_huffman_lengths(const uint32_t* counts, int32_t n, int32_t limit, uint8_t* lengths) {
@@ -708,21 +661,16 @@ extern "C" int cgan_png_encode_u8_level(const uint8_t* in, int32_t n, int32_t h,
   CGAN_REQUIRE(in && out && sizes && workspace, "cgan_png_encode_u8: null pointer");
   CGAN_REQUIRE(level == 1 || level == 2, "cgan_png_encode_u8: level = %d: 1 (fixed Huffman) or 2 (per-row choice) only", level);
   if (!png_shape_ok("cgan_png_encode_u8", n, h, w, c)) return CGAN_ERR_BAD_ARG;
-  CGAN_REQUIRE(out_pitch >= cgan_png_bound_bytes(h, w, c), "cgan_png_encode_u8: out_pitch %zu is below the bound %zu",
-               out_pitch, cgan_png_bound_bytes(h, w, c));
-  if (workspace_bytes < cgan_png_workspace_bytes(n, h, w, c) || (reinterpret_cast<uintptr_t>(workspace) & 15u)) {
-    cgan_set_error("cgan_png_encode_u8: workspace of %zu bytes (16-byte aligned) expected, got %zu at %p",
-                   cgan_png_workspace_bytes(n, h, w, c), workspace_bytes, workspace);
-    return CGAN_ERR_WORKSPACE;
-  }
+  if (const int rc = row_files::buffers_ok("cgan_png_encode_u8", out_pitch, cgan_png_bound_bytes(h, w, c), workspace,
+                                          workspace_bytes, cgan_png_workspace_bytes(n, h, w, c)))
+    return rc;
   const uint32_t m = (uint32_t)w * c + 1u;
-  const size_t tb = png_table_bytes((int64_t)n * h);
-  uint8_t* ws = static_cast<uint8_t*>(workspace);
-  uint32_t* row_size = reinterpret_cast<uint32_t*>(ws);
-  uint32_t* row_s1 = reinterpret_cast<uint32_t*>(ws + tb);
-  uint32_t* row_s2 = reinterpret_cast<uint32_t*>(ws + 2 * tb);
-  uint32_t* row_off = reinterpret_cast<uint32_t*>(ws + 3 * tb);
-  uint8_t* staging = ws + 4 * tb;
+  const int64_t all_rows = (int64_t)n * h;
+  uint32_t* row_size = row_files::table(workspace, all_rows, 0);
+  uint32_t* row_s1 = row_files::table(workspace, all_rows, 1);
+  uint32_t* row_s2 = row_files::table(workspace, all_rows, 2);
+  uint32_t* row_off = row_files::table(workspace, all_rows, 3);
+  uint8_t* staging = reinterpret_cast<uint8_t*>(row_files::table(workspace, all_rows, 4));
   const uint32_t slot = png_slot_bytes(m);
   const PngLds lds = png_lds(m);
   auto* rows = level == 2 ? &png_rows_kernel<2> : &png_rows_kernel<1>;
@@ -738,12 +686,12 @@ extern "C" int cgan_png_encode_u8_level(const uint8_t* in, int32_t n, int32_t h,
     attr_set[level - 1] = true;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rows, dim3(h, n), dim3(PNG_T), lds_bytes, s, in, h, w * c, c, row_size, row_s1, row_s2, staging, slot);
+  hipLaunchKernelGGL(rows, dim3(h, n), dim3(T), lds_bytes, s, in, h, w * c, c, row_size, row_s1, row_s2, staging, slot);
   CGAN_CHECK_LAUNCH("cgan_png_encode_u8 (rows)");
-  hipLaunchKernelGGL(png_finish_kernel, dim3(n), dim3(PNG_T), 0, s, h, w, c, row_size, row_s1, row_s2, row_off, out,
+  hipLaunchKernelGGL(png_finish_kernel, dim3(n), dim3(T), 0, s, h, w, c, row_size, row_s1, row_s2, row_off, out,
                      out_pitch, reinterpret_cast<long long*>(sizes));
   CGAN_CHECK_LAUNCH("cgan_png_encode_u8 (finish)");
-  hipLaunchKernelGGL(png_gather_kernel, dim3(h, n), dim3(PNG_T), 0, s, h, row_size, row_off, staging, slot, out, out_pitch);
+  hipLaunchKernelGGL(png_gather_kernel, dim3(h, n), dim3(T), 0, s, h, row_size, row_off, staging, slot, out, out_pitch);
   CGAN_CHECK_LAUNCH("cgan_png_encode_u8 (gather)");
   return CGAN_OK;
 }

@@ -643,59 +643,13 @@ def binarize(x: torch.Tensor, threshold: float, want_float: bool = True, want_ui
 
 
 PNG_MAX_WIDTH = 4096         # the widest row cgan_png_encode_u8 takes (pixels, grey or RGB)
-
-
-def png_bound_bytes(h: int, w: int, c: int) -> int:
-    """The most bytes the PNG file of one [h, w, c] image can have (``png_encode``'s row pitch)."""
-    bound = _lib.load().cgan_png_bound_bytes(int(h), int(w), int(c))
-    if bound == 0:
-        _lib.check(-1, "cgan_png_bound_bytes")
-    return bound
-
-
-def png_encode(img_u8: torch.Tensor, level: int = 1):
-    """uint8 [N, H, W, C] device tensor (contiguous, C = 1 grey or 3 RGB, W <= PNG_MAX_WIDTH) -> (buf uint8 [N, bound],
-    sizes int64 [N]): ``buf[i, :sizes[i]]`` is the complete PNG file of image i (DESIGN 4.17).  Both stay on the device and
-    nothing is synchronised; everything else is refused here, before any launch.  ``level`` 1: fixed-Huffman blocks;
-    2: per row the smallest of a fixed, a dynamic and a stored block (smaller files, same pixels, same bound)."""
-    _need_cuda(img_u8)
-    if level not in (1, 2):
-        raise RuntimeError("png_encode: level %r: 1 or 2 expected" % (level,))
-    if img_u8.dtype != torch.uint8:
-        raise RuntimeError("png_encode: uint8 input expected, got %s" % img_u8.dtype)
-    if img_u8.dim() != 4 or img_u8.shape[3] not in (1, 3):
-        raise RuntimeError("png_encode: [N, H, W, C] with C = 1 (grey) or 3 (RGB) expected, got %s" % (tuple(img_u8.shape),))
-    if not img_u8.is_contiguous():
-        raise RuntimeError("png_encode: a contiguous tensor is expected (strides %s)" % (img_u8.stride(),))
-    n, h, w, c = img_u8.shape
-    if w > PNG_MAX_WIDTH:
-        raise RuntimeError("png_encode: width %d exceeds the %d pixels per row the encoder supports" % (w, PNG_MAX_WIDTH))
-    if n < 1 or h < 1 or w < 1:
-        raise RuntimeError("png_encode: empty input %s" % (tuple(img_u8.shape),))
-    lib = _lib.load()
-    bound = png_bound_bytes(h, w, c)
-    nbytes = lib.cgan_png_workspace_bytes(n, h, w, c)
-    if nbytes == 0:
-        _lib.check(-1, "cgan_png_workspace_bytes")
-    ws = _empty(nbytes, dtype=torch.uint8, device=img_u8.device)
-    buf = _empty((n, bound), dtype=torch.uint8, device=img_u8.device)
-    sizes = _empty((n,), dtype=torch.int64, device=img_u8.device)
-    _lib.check(lib.cgan_png_encode_u8_level(_ptr(img_u8), n, h, w, c, int(level), _ptr(buf), bound, _ptr(sizes), _ptr(ws),
-                                            nbytes, _stream()), "cgan_png_encode_u8_level")
-    return buf, sizes
-
-
 JPEG_MAX_WIDTH = 4096        # the widest image cgan_jpeg_encode_u8 takes (pixels, grey or RGB)
 JPEG_SUBSAMPLINGS = ("444", "420")
 
 
-def _jpeg_args(what, img_u8, quality, subsampling):
-    """Refuses what the JPEG entry points do not take, before any launch -> (n, h, w, c, quality, subsampling as int)."""
+def _u8_batch(what, img_u8, max_width):
+    """Refuses what the image encoders do not take as a batch, before any launch -> (n, h, w, c)."""
     _need_cuda(img_u8)
-    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
-        raise RuntimeError("%s: quality %r: an integer from 1 to 100 expected" % (what, quality))
-    if str(subsampling) not in JPEG_SUBSAMPLINGS:
-        raise RuntimeError("%s: subsampling %r: '444' or '420' expected" % (what, subsampling))
     if img_u8.dtype != torch.uint8:
         raise RuntimeError("%s: uint8 input expected, got %s" % (what, img_u8.dtype))
     if img_u8.dim() != 4 or img_u8.shape[3] not in (1, 3):
@@ -703,19 +657,62 @@ def _jpeg_args(what, img_u8, quality, subsampling):
     if not img_u8.is_contiguous():
         raise RuntimeError("%s: a contiguous tensor is expected (strides %s)" % (what, img_u8.stride()))
     n, h, w, c = img_u8.shape
-    if w > JPEG_MAX_WIDTH:
-        raise RuntimeError("%s: width %d exceeds the %d pixels the encoder supports" % (what, w, JPEG_MAX_WIDTH))
+    if w > max_width:
+        raise RuntimeError("%s: width %d exceeds the %d pixels per row the encoder supports" % (what, w, max_width))
     if n < 1 or h < 1 or w < 1:
         raise RuntimeError("%s: empty input %s" % (what, tuple(img_u8.shape)))
+    return n, h, w, c
+
+
+def _size(nbytes, what):
+    """A size the library returns, 0 meaning an error: the size, or the library's message raised."""
+    if nbytes == 0:
+        _lib.check(-1, what)
+    return nbytes
+
+
+def _file_buffers(img_u8, bound, nbytes):
+    """-> (workspace uint8 [nbytes], buf uint8 [N, bound], sizes int64 [N]) on the images' device, nothing initialised."""
+    n, dev = img_u8.shape[0], img_u8.device
+    return (_empty(nbytes, dtype=torch.uint8, device=dev), _empty((n, bound), dtype=torch.uint8, device=dev),
+            _empty((n,), dtype=torch.int64, device=dev))
+
+
+def png_bound_bytes(h: int, w: int, c: int) -> int:
+    """The most bytes the PNG file of one [h, w, c] image can have (``png_encode``'s row pitch)."""
+    return _size(_lib.load().cgan_png_bound_bytes(int(h), int(w), int(c)), "cgan_png_bound_bytes")
+
+
+def png_encode(img_u8: torch.Tensor, level: int = 1):
+    """uint8 [N, H, W, C] device tensor (contiguous, C = 1 grey or 3 RGB, W <= PNG_MAX_WIDTH) -> (buf uint8 [N, bound],
+    sizes int64 [N]): ``buf[i, :sizes[i]]`` is the complete PNG file of image i (DESIGN 4.17).  Both stay on the device and
+    nothing is synchronised; everything else is refused here, before any launch.  ``level`` 1: fixed-Huffman blocks;
+    2: per row the smallest of a fixed, a dynamic and a stored block (smaller files, same pixels, same bound)."""
+    n, h, w, c = _u8_batch("png_encode", img_u8, PNG_MAX_WIDTH)
+    if level not in (1, 2):
+        raise RuntimeError("png_encode: level %r: 1 or 2 expected" % (level,))
+    lib = _lib.load()
+    bound = png_bound_bytes(h, w, c)
+    nbytes = _size(lib.cgan_png_workspace_bytes(n, h, w, c), "cgan_png_workspace_bytes")
+    ws, buf, sizes = _file_buffers(img_u8, bound, nbytes)
+    _lib.check(lib.cgan_png_encode_u8_level(_ptr(img_u8), n, h, w, c, int(level), _ptr(buf), bound, _ptr(sizes), _ptr(ws),
+                                            nbytes, _stream()), "cgan_png_encode_u8_level")
+    return buf, sizes
+
+
+def _jpeg_args(what, img_u8, quality, subsampling):
+    """Refuses what the JPEG entry points do not take, before any launch -> (n, h, w, c, quality, subsampling as int)."""
+    n, h, w, c = _u8_batch(what, img_u8, JPEG_MAX_WIDTH)
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise RuntimeError("%s: quality %r: an integer from 1 to 100 expected" % (what, quality))
+    if str(subsampling) not in JPEG_SUBSAMPLINGS:
+        raise RuntimeError("%s: subsampling %r: '444' or '420' expected" % (what, subsampling))
     return n, h, w, c, quality, int(str(subsampling))
 
 
 def jpeg_bound_bytes(h: int, w: int, c: int, subsampling="444") -> int:
     """The most bytes the JPEG file of one [h, w, c] image can have (``jpeg_encode``'s row pitch)."""
-    bound = _lib.load().cgan_jpeg_bound_bytes(int(h), int(w), int(c), int(str(subsampling)))
-    if bound == 0:
-        _lib.check(-1, "cgan_jpeg_bound_bytes")
-    return bound
+    return _size(_lib.load().cgan_jpeg_bound_bytes(int(h), int(w), int(c), int(str(subsampling))), "cgan_jpeg_bound_bytes")
 
 
 def jpeg_encode(img_u8: torch.Tensor, quality: int = 90, subsampling="444"):
@@ -726,12 +723,8 @@ def jpeg_encode(img_u8: torch.Tensor, quality: int = 90, subsampling="444"):
     n, h, w, c, quality, sub = _jpeg_args("jpeg_encode", img_u8, quality, subsampling)
     lib = _lib.load()
     bound = jpeg_bound_bytes(h, w, c, sub)
-    nbytes = lib.cgan_jpeg_workspace_bytes(n, h, w, c, sub)
-    if nbytes == 0:
-        _lib.check(-1, "cgan_jpeg_workspace_bytes")
-    ws = _empty(nbytes, dtype=torch.uint8, device=img_u8.device)
-    buf = _empty((n, bound), dtype=torch.uint8, device=img_u8.device)
-    sizes = _empty((n,), dtype=torch.int64, device=img_u8.device)
+    nbytes = _size(lib.cgan_jpeg_workspace_bytes(n, h, w, c, sub), "cgan_jpeg_workspace_bytes")
+    ws, buf, sizes = _file_buffers(img_u8, bound, nbytes)
     _lib.check(lib.cgan_jpeg_encode_u8(_ptr(img_u8), n, h, w, c, quality, sub, _ptr(buf), bound, _ptr(sizes), _ptr(ws),
                                        nbytes, _stream()), "cgan_jpeg_encode_u8")
     return buf, sizes

@@ -1,49 +1,16 @@
-"""PNG files from uint8 device images: ``ops.png_encode`` (csrc/png.hip) builds the files on the device, this
-module brings their bytes to the host and writes them.  There is no host encoder behind it: a CPU tensor is refused.
-
-Only the compressed bytes cross PCIe.  How many they are is known on the device alone, so a batch costs two waits: one for
-the N file lengths (8 N bytes; this is where the host waits for the encoder), one for a single copy of the first
-``max(lengths)`` bytes of every row of the output buffer into pinned memory.
+"""PNG files from uint8 device images: ``ops.png_encode`` (csrc/png.hip) builds the files on the device,
+``_files`` brings their bytes to the host (two waits, only the compressed bytes cross PCIe) and writes them.  There is no
+host encoder behind it: a CPU tensor is refused.
 """
-import torch
-
-from . import ops
-
-_PINNED = None
-
-
-def _pinned(nbytes):
-    """A pinned staging buffer, kept and grown between calls (pinning memory costs far more than the copy it serves)."""
-    global _PINNED
-    if _PINNED is None or _PINNED.numel() < nbytes:
-        _PINNED = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
-    return _PINNED[:nbytes]
-
-
-def _fetch(img_u8, level):
-    """-> (host uint8 array [N, max length] in the pinned buffer, list of N lengths); valid until the next call."""
-    buf, sizes = ops.png_encode(img_u8, level)
-    lengths = sizes.cpu().tolist()
-    n, longest = buf.shape[0], max(lengths)
-    host = _pinned(n * longest).view(n, longest)
-    host.copy_(buf[:, :longest], non_blocking=True)
-    torch.cuda.current_stream(img_u8.device).synchronize()
-    return host.numpy(), lengths
+from . import _files, ops
 
 
 def encode(img_u8, level=1):
     """uint8 [N, H, W, C] device tensor (C = 1 or 3) -> list of N ``bytes``, each a complete PNG file.  ``level``: see
     ``ops.png_encode``."""
-    host, lengths = _fetch(img_u8, level)
-    return [host[i, :k].tobytes() for i, k in enumerate(lengths)]
+    return _files.to_bytes(*_files.fetch(*ops.png_encode(img_u8, level)))
 
 
 def write(img_u8, paths, level=1):
     """Encode a batch on the device (at ``level``, see ``ops.png_encode``) and write image i to ``paths[i]``."""
-    paths = list(paths)
-    if len(paths) != img_u8.shape[0]:
-        raise ValueError("png.write: %d images but %d paths" % (img_u8.shape[0], len(paths)))
-    host, lengths = _fetch(img_u8, level)
-    for i, (path, k) in enumerate(zip(paths, lengths)):
-        with open(path, "wb") as f:
-            f.write(memoryview(host[i, :k]))
+    _files.write_files("png.write", *_files.fetch(*ops.png_encode(img_u8, level)), paths)

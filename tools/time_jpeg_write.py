@@ -11,22 +11,16 @@ and ends when the last file is closed; the paths alternate inside each repetitio
 minimum and maximum.  Prints seconds per image and bytes per image for every path, the PSNR of the device files and of PIL's
 against the source pixels, and one JSON line.
 """
-import argparse
-import json
-import statistics
 import sys
-import tempfile
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import numpy as np
-import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tools"))
 
-from time_png_write import BATCH, SIZE, THREADS, outputs, timed  # noqa: E402
+from time_png_write import BATCH, finish, measure, setup  # noqa: E402
 
 QUALITY = 90
 
@@ -37,26 +31,13 @@ def psnr(a, b):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--out", default=None, help="directory to write into (default: a temporary one)")
-    ap.add_argument("--reps", type=int, default=9)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--json", default=None, help="also write the result line to this file")
-    args = ap.parse_args()
+    args, dev, host, out, tmp, pool = setup(__doc__, "time_jpeg_write")
     from PIL import Image
 
     from climategan_amd import jpeg, png
 
-    if not torch.cuda.is_available():
-        raise SystemExit("time_jpeg_write: needs the GPU (nothing here can be timed on a CPU)")
-    dev = outputs()
-    host = dev.cpu().numpy()
-    tmp = tempfile.TemporaryDirectory() if args.out is None else None
-    out = Path(tmp.name if tmp else args.out)
-    out.mkdir(parents=True, exist_ok=True)
     kinds = ("gpu_jpeg_444", "gpu_jpeg_420", "gpu_png_level2", "pil_jpeg_444", "pil_jpeg_420")
     paths = {k: [out / ("%s_%02d.%s" % (k, i, "png" if "png" in k else "jpg")) for i in range(BATCH)] for k in kinds}
-    pool = ThreadPoolExecutor(THREADS)
 
     def pil(kind, subsampling):
         list(pool.map(lambda ip: Image.fromarray(ip[0]).save(ip[1], "JPEG", quality=QUALITY, subsampling=subsampling),
@@ -67,22 +48,8 @@ def main():
             "gpu_png_level2": lambda: png.write(dev, paths["gpu_png_level2"], level=2),
             "pil_jpeg_444": lambda: pil("pil_jpeg_444", 0),
             "pil_jpeg_420": lambda: pil("pil_jpeg_420", 2)}
-    times = {k: [] for k in runs}
-    d2h = []
-    for rep in range(args.warmup + args.reps):
-        for k, fn in runs.items():
-            t = timed(fn)
-            if rep >= args.warmup:
-                times[k].append(t)
-        t = timed(lambda: dev.cpu())
-        if rep >= args.warmup:
-            d2h.append(t)
-    res = {"batch": BATCH, "shape": [SIZE, SIZE, 3], "quality": QUALITY, "reps": args.reps, "threads": THREADS,
-           "raw_d2h_s_per_image": statistics.median(d2h) / BATCH}
+    res = measure(args, dev, runs, paths, quality=QUALITY)
     for k in runs:
-        res[k] = {"s_per_image": statistics.median(times[k]) / BATCH,
-                  "s_per_image_min_max": [min(times[k]) / BATCH, max(times[k]) / BATCH],
-                  "bytes_per_image": sum(p.stat().st_size for p in paths[k]) / BATCH}
         decoded = np.stack([np.asarray(Image.open(p)) for p in paths[k]])          # every file opens; PNG holds the pixels
         res[k]["psnr_db"] = psnr(decoded, host)
         print("%-15s %.6f s/image (min %.6f, max %.6f)  %8.0f bytes/image  PSNR %.2f dB" % (
@@ -98,14 +65,7 @@ def main():
         print("%s: bytes JPEG / PNG level 2 = %.4f, JPEG / PIL's JPEG = %.4f; time JPEG / PNG level 2 = %.3f, PIL / JPEG = %.2f"
               % (sub, res["size_ratio_jpeg_%s_over_png_level2" % sub], res["size_ratio_jpeg_%s_over_pil" % sub],
                  res["time_ratio_jpeg_%s_over_png_level2" % sub], res["speedup_jpeg_%s_over_pil" % sub]))
-    line = json.dumps(res)
-    print(line)
-    if args.json:
-        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.json).write_text(line + "\n")
-    pool.shutdown()
-    if tmp:
-        tmp.cleanup()
+    finish(args, res, tmp, pool)
 
 
 if __name__ == "__main__":

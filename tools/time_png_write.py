@@ -70,34 +70,27 @@ def timed(fn):
     return time.perf_counter() - t0
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+def setup(doc, name):
+    """What both write-timing tools start with -> (args, uint8 batch on the device, the same as a host array, output
+    directory, its TemporaryDirectory or None, the PIL thread pool)."""
+    ap = argparse.ArgumentParser(description=doc.split("\n")[0])
     ap.add_argument("--out", default=None, help="directory to write into (default: a temporary one)")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--json", default=None, help="also write the result line to this file")
     args = ap.parse_args()
-    from PIL import Image
-
-    from climategan_amd import png
-
     if not torch.cuda.is_available():
-        raise SystemExit("time_png_write: needs the GPU (nothing here can be timed on a CPU)")
+        raise SystemExit("%s: needs the GPU (nothing here can be timed on a CPU)" % name)
     dev = outputs()
-    host = dev.cpu().numpy()
     tmp = tempfile.TemporaryDirectory() if args.out is None else None
     out = Path(tmp.name if tmp else args.out)
     out.mkdir(parents=True, exist_ok=True)
-    paths = {k: [out / ("%s_%02d.png" % (k, i)) for i in range(BATCH)] for k in ("gpu", "gpu_level2", "pil_default", "pil_level1")}
-    pool = ThreadPoolExecutor(THREADS)
+    return args, dev, dev.cpu().numpy(), out, tmp, ThreadPoolExecutor(THREADS)
 
-    def pil(kind, **kw):
-        list(pool.map(lambda ip: Image.fromarray(ip[0]).save(ip[1], **kw), zip(host, paths[kind])))
 
-    runs = {"gpu": lambda: png.write(dev, paths["gpu"]),
-            "gpu_level2": lambda: png.write(dev, paths["gpu_level2"], level=2),
-            "pil_default": lambda: pil("pil_default"),
-            "pil_level1": lambda: pil("pil_level1", compress_level=1)}
+def measure(args, dev, runs, paths, **extra):
+    """The paths of ``runs`` alternating inside each repetition, the raw device-to-host copy timed beside them -> the result
+    dictionary: per path the median, minimum and maximum seconds per image and the bytes per image of its files."""
     times = {k: [] for k in runs}
     d2h = []
     for rep in range(args.warmup + args.reps):
@@ -108,15 +101,46 @@ def main():
         t = timed(lambda: dev.cpu())
         if rep >= args.warmup:
             d2h.append(t)
-    for i in range(BATCH):                                   # the device files hold the same pixels
-        assert np.array_equal(np.asarray(Image.open(paths["gpu"][i])), host[i]), i
-        assert np.array_equal(np.asarray(Image.open(paths["gpu_level2"][i])), host[i]), i
-    res = {"batch": BATCH, "shape": [SIZE, SIZE, 3], "reps": args.reps, "threads": THREADS,
+    res = {"batch": BATCH, "shape": [SIZE, SIZE, 3], **extra, "reps": args.reps, "threads": THREADS,
            "raw_d2h_s_per_image": statistics.median(d2h) / BATCH}
     for k in runs:
         res[k] = {"s_per_image": statistics.median(times[k]) / BATCH,
                   "s_per_image_min_max": [min(times[k]) / BATCH, max(times[k]) / BATCH],
                   "bytes_per_image": sum(p.stat().st_size for p in paths[k]) / BATCH}
+    return res
+
+
+def finish(args, res, tmp, pool):
+    line = json.dumps(res)
+    print(line)
+    if args.json:
+        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.json).write_text(line + "\n")
+    pool.shutdown()
+    if tmp:
+        tmp.cleanup()
+
+
+def main():
+    args, dev, host, out, tmp, pool = setup(__doc__, "time_png_write")
+    from PIL import Image
+
+    from climategan_amd import png
+
+    paths = {k: [out / ("%s_%02d.png" % (k, i)) for i in range(BATCH)] for k in ("gpu", "gpu_level2", "pil_default", "pil_level1")}
+
+    def pil(kind, **kw):
+        list(pool.map(lambda ip: Image.fromarray(ip[0]).save(ip[1], **kw), zip(host, paths[kind])))
+
+    runs = {"gpu": lambda: png.write(dev, paths["gpu"]),
+            "gpu_level2": lambda: png.write(dev, paths["gpu_level2"], level=2),
+            "pil_default": lambda: pil("pil_default"),
+            "pil_level1": lambda: pil("pil_level1", compress_level=1)}
+    res = measure(args, dev, runs, paths)
+    for i in range(BATCH):                                   # the device files hold the same pixels
+        assert np.array_equal(np.asarray(Image.open(paths["gpu"][i])), host[i]), i
+        assert np.array_equal(np.asarray(Image.open(paths["gpu_level2"][i])), host[i]), i
+    for k in runs:
         print("%-12s %.6f s/image (min %.6f, max %.6f)  %.0f bytes/image" % (
             k, res[k]["s_per_image"], *res[k]["s_per_image_min_max"], res[k]["bytes_per_image"]))
     res["size_ratio_gpu_over_pil_default"] = res["gpu"]["bytes_per_image"] / res["pil_default"]["bytes_per_image"]
@@ -127,14 +151,7 @@ def main():
         res["size_ratio_level2_over_level1"], res["size_ratio_level2_over_pil_default"]))
     res["speedup_gpu_over_pil_default"] = res["pil_default"]["s_per_image"] / res["gpu"]["s_per_image"]
     res["speedup_gpu_over_pil_level1"] = res["pil_level1"]["s_per_image"] / res["gpu"]["s_per_image"]
-    line = json.dumps(res)
-    print(line)
-    if args.json:
-        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.json).write_text(line + "\n")
-    pool.shutdown()
-    if tmp:
-        tmp.cleanup()
+    finish(args, res, tmp, pool)
 
 
 if __name__ == "__main__":
