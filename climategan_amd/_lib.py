@@ -218,8 +218,7 @@ _SIGNATURES = {
                                                  C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "cgan_painter_heads_diffaug_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, C.c_int32, C.c_int32, _P, _P]),
-    "cgan_data_transform": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
-    "cgan_data_transform_raw": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P]),
+    "cgan_data_transform": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P]),
     "cgan_data_source_minmax": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "cgan_data_jitter": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "cgan_avgpool3x3s2_bwd_nhwc": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

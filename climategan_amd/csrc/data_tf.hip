@@ -4,9 +4,9 @@
 //                         sequence of flips, crops and resizes to at most two resampling stages with an integer index map
 //                         before, between and after them (include/climategan_hip.h); the kernel walks that plan backwards
 //                         from the output pixel and touches only the source pixels the final window needs.
-//   cgan_data_transform_raw  the same with the raw source kinds of the nearest mode: tensor_loader's decode (data.py:91-148,
-//                         231-252, 344-399; tutils.py:195-293) applied to the gathered pixel before the store, so that a
-//                         160 x 160 task decodes 1 % of a 1200 x 1800 source and the upload is the file's own bytes.
+//                         With a raw source kind (nearest mode) tensor_loader's decode (data.py:91-148, 231-252, 344-399;
+//                         tutils.py:195-293) is applied to the gathered pixel before the store, so that a 160 x 160 task
+//                         decodes 1 % of a 1200 x 1800 source and the upload is the file's own bytes.
 //   cgan_data_source_minmax  the one thing that has to see the whole source: min / max for the normalised depth modes, x and
 //                         the mask's "max > 127", as fixed-range partials over 16-byte non-temporal loads and a fixed-order
 //                         finish that leaves (min, range, max, flag) where the gather's items point.
@@ -25,6 +25,8 @@
 // x, four pixels per thread for the one-tap maps), non-temporal stores (the output is written once and read by a later
 // launch at the earliest).  No atomics, no LDS outside the contrast reduction.
 #include "cgan_common.h"
+
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -80,42 +82,6 @@ __device__ __forceinline__ int bucket_of(float v, const float* __restrict__ b, i
     else hi = mid;
   }
   return lo;
-}
-
-constexpr int kNearPix = 4;   // output pixels per thread: that many loads in flight
-
-template <typename E, int NS, bool BUCKET>
-__global__ __launch_bounds__(256) void data_tf_nearest_kernel(const CganDataTfItem* __restrict__ items,
-                                                              const float* __restrict__ bounds, int n_bounds) {
-  const CganDataTfItem it = items[blockIdx.y];
-  const int ohw = it.out_h * it.out_w;
-  const int p0 = blockIdx.x * (256 * kNearPix) + threadIdx.x;
-  if (p0 >= ohw) return;
-  const E* src = reinterpret_cast<const E*>(it.src);
-  int off[kNearPix];
-#pragma unroll
-  for (int k = 0; k < kNearPix; ++k) {
-    const int p = p0 + k * 256;
-    const int pc = p < ohw ? p : p0;          // a thread past the end repeats its first pixel and does not store
-    const int oy = pc / it.out_w, ox = pc - oy * it.out_w;
-    off[k] = near_offset<NS>(it, oy, ox);
-  }
-  for (int c = 0; c < it.channels; ++c) {
-    E v[kNearPix];
-#pragma unroll
-    for (int k = 0; k < kNearPix; ++k) v[k] = src[c * it.stride_c + off[k]];
-#pragma unroll
-    for (int k = 0; k < kNearPix; ++k) {
-      const int p = p0 + k * 256;
-      if (p >= ohw) continue;
-      if constexpr (BUCKET) {
-        const int32_t b = bucket_of(__builtin_bit_cast(float, v[k]), bounds, n_bounds);
-        CGAN_ST_STREAM(b, reinterpret_cast<int32_t*>(it.dst) + c * ohw + p);
-      } else {
-        CGAN_ST_STREAM(v[k], reinterpret_cast<E*>(it.dst) + c * ohw + p);
-      }
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------------ raw sources
@@ -190,38 +156,72 @@ __device__ __forceinline__ float decode_raw(uint32_t raw, const RawConsts& k, co
   }
 }
 
+// ------------------------------------------------------------------------------------------------ the nearest gather
+// The source policy is KIND: CGAN_DTF_SRC_B4 / B8 gather every channel's 4- or 8-byte element as it is; a raw kind reads one
+// pixel (all the channels of its code) and writes the one channel it decodes to.
+template <int KIND>
+struct NearSource {
+  static constexpr bool kRaw = KIND >= CGAN_DTF_SRC_UNITY_D;
+  using Elem = std::conditional_t<KIND == CGAN_DTF_SRC_B8, uint64_t, uint32_t>;
+  static __device__ __forceinline__ int channels(const CganDataTfItem& it) { return kRaw ? 1 : it.channels; }
+  static __device__ __forceinline__ Elem load(const CganDataTfItem& it, int off, int c) {
+    if constexpr (kRaw) return load_raw<KIND>(it.src, off, it.stride_c);
+    else return reinterpret_cast<const Elem*>(it.src)[c * it.stride_c + off];
+  }
+};
+
+constexpr int kNearPix = 4;   // output pixels per thread: that many loads in flight
+
 template <int KIND, int NS, bool BUCKET>
-__global__ __launch_bounds__(256) void data_tf_decode_kernel(const CganDataTfItem* __restrict__ items,
-                                                             const float* __restrict__ bounds, int n_bounds,
-                                                             CganDataTfPalette pal) {
+__global__ __launch_bounds__(256) void data_tf_nearest_kernel(const CganDataTfItem* __restrict__ items,
+                                                              const float* __restrict__ bounds, int n_bounds,
+                                                              CganDataTfPalette pal) {
+  using S = NearSource<KIND>;
+  using E = typename S::Elem;
   const CganDataTfItem it = items[blockIdx.y];
   const int ohw = it.out_h * it.out_w;
   const int p0 = blockIdx.x * (256 * kNearPix) + threadIdx.x;
   if (p0 >= ohw) return;
-  uint32_t raw[kNearPix];
+  int off[kNearPix];
+  E v[kNearPix];
 #pragma unroll
   for (int k = 0; k < kNearPix; ++k) {
     const int p = p0 + k * 256;
-    const int pc = p < ohw ? p : p0;
+    const int pc = p < ohw ? p : p0;          // a thread past the end repeats its first pixel and does not store
     const int oy = pc / it.out_w, ox = pc - oy * it.out_w;
-    raw[k] = load_raw<KIND>(it.src, near_offset<NS>(it, oy, ox), it.stride_c);
+    off[k] = near_offset<NS>(it, oy, ox);
+    // a raw kind's one pixel is loaded next to its offset: its 3 or 4 byte addresses die before the next pixel's are formed
+    // (2 VGPRs less for the SEG kinds than loading after the loop)
+    if constexpr (S::kRaw) v[k] = S::load(it, off[k], 0);
   }
   RawConsts kc = {it.u8_min, it.u8_range, it.far_plane, it.dec_flags};
-  if (it.stats) {   // written by cgan_data_source_minmax earlier on this stream
+  if (S::kRaw && it.stats) {   // written by cgan_data_source_minmax earlier on this stream
     kc.mn = it.stats[0], kc.rng = it.stats[1];
     kc.flags = (kc.flags & ~CGAN_DTF_DEC_THRESHOLD) | (it.stats[3] != 0.f ? CGAN_DTF_DEC_THRESHOLD : 0);
   }
+  for (int c = 0; c < S::channels(it); ++c) {
+    if constexpr (!S::kRaw) {
 #pragma unroll
-  for (int k = 0; k < kNearPix; ++k) {
-    const int p = p0 + k * 256;
-    if (p >= ohw) continue;
-    const float v = decode_raw<KIND>(raw[k], kc, pal);
-    if constexpr (BUCKET) {
-      CGAN_ST_STREAM((int32_t)bucket_of(v, bounds, n_bounds), reinterpret_cast<int32_t*>(it.dst) + p);
-    } else if constexpr (KIND == CGAN_DTF_SRC_SEG_EXACT) {
-      CGAN_ST_STREAM((double)v, reinterpret_cast<double*>(it.dst) + p);   // torch.tensor(np.ones(...) * 14): float64
-    } else {
-      CGAN_ST_STREAM(v, reinterpret_cast<float*>(it.dst) + p);
+      for (int k = 0; k < kNearPix; ++k) v[k] = S::load(it, off[k], c);
+    }
+#pragma unroll
+    for (int k = 0; k < kNearPix; ++k) {
+      const int p = p0 + k * 256, o = c * ohw + p;
+      if (p >= ohw) continue;
+      if constexpr (!S::kRaw && !BUCKET) {
+        CGAN_ST_STREAM(v[k], reinterpret_cast<E*>(it.dst) + o);
+      } else {
+        float f;
+        if constexpr (S::kRaw) f = decode_raw<KIND>(v[k], kc, pal);
+        else f = __builtin_bit_cast(float, v[k]);
+        if constexpr (BUCKET) {
+          CGAN_ST_STREAM((int32_t)bucket_of(f, bounds, n_bounds), reinterpret_cast<int32_t*>(it.dst) + o);
+        } else if constexpr (KIND == CGAN_DTF_SRC_SEG_EXACT) {
+          CGAN_ST_STREAM((double)f, reinterpret_cast<double*>(it.dst) + o);   // torch.tensor(np.ones(...) * 14): float64
+        } else {
+          CGAN_ST_STREAM(f, reinterpret_cast<float*>(it.dst) + o);
+        }
+      }
     }
   }
 }
@@ -474,6 +474,15 @@ __global__ __launch_bounds__(256) void jitter_kernel(const float* __restrict__ x
   }
 }
 
+// A run-time choice as a template argument: calls f(std::integral_constant<int, v>) for v in [0, N)
+template <int N, typename F>
+void static_int(int v, F&& f) {
+  if constexpr (N > 0) {
+    if (v == N - 1) f(std::integral_constant<int, N - 1>{});
+    else static_int<N - 1>(v, f);
+  }
+}
+
 bool window_inside(const CganDataTfMap& m, int wh, int ww, int H, int W) {
   if (m.row_off < 0 || (long)m.row_off + wh > H) return false;
   if (m.flip) return m.col_off <= W - 1 && (long)m.col_off - (ww - 1) >= 0;
@@ -484,15 +493,8 @@ bool window_inside(const CganDataTfMap& m, int wh, int ww, int H, int W) {
 
 extern "C" int cgan_data_transform(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count,
                                    int32_t mode, int32_t src_kind, int32_t epilogue, const float* mean, const float* std,
-                                   const float* boundaries, int32_t n_boundaries, void* stream) {
-  return cgan_data_transform_raw(items_host, items_device, count, mode, src_kind, epilogue, mean, std, boundaries,
-                                 n_boundaries, nullptr, stream);
-}
-
-extern "C" int cgan_data_transform_raw(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count,
-                                       int32_t mode, int32_t src_kind, int32_t epilogue, const float* mean, const float* std,
-                                       const float* boundaries, int32_t n_boundaries, const CganDataTfPalette* palette,
-                                       void* stream) {
+                                   const float* boundaries, int32_t n_boundaries, const CganDataTfPalette* palette,
+                                   void* stream) {
   CGAN_REQUIRE(items_host && items_device && count > 0 && count <= 65535, "data_transform: bad item table");
   CGAN_REQUIRE(mode == CGAN_DTF_NEAREST || mode == CGAN_DTF_BILINEAR, "data_transform: bad mode %d", mode);
   CGAN_REQUIRE(src_kind >= CGAN_DTF_SRC_B4 && src_kind <= CGAN_DTF_SRC_SEG_NEAREST, "data_transform: bad source kind %d",
@@ -586,43 +588,29 @@ extern "C" int cgan_data_transform_raw(const CganDataTfItem* items_host, const C
   hipStream_t s = (hipStream_t)stream;
   if (mode == CGAN_DTF_NEAREST) {
     const dim3 grid((unsigned)((max_pix + 256 * kNearPix - 1) / (256 * kNearPix)), count);
-#define NEAR(E, NS, B) \
-  hipLaunchKernelGGL((data_tf_nearest_kernel<E, NS, B>), grid, dim3(256), 0, s, items_device, boundaries, n_boundaries)
-#define NEAR_NS(E, B) \
-  do { if (ns == 0) NEAR(E, 0, B); else if (ns == 1) NEAR(E, 1, B); else NEAR(E, 2, B); } while (0)
-#define DEC(K, NS, B) \
-  hipLaunchKernelGGL((data_tf_decode_kernel<K, NS, B>), grid, dim3(256), 0, s, items_device, boundaries, n_boundaries, pal)
-#define DEC_NS(K, B) \
-  do { if (ns == 0) DEC(K, 0, B); else if (ns == 1) DEC(K, 1, B); else DEC(K, 2, B); } while (0)
-#define DEC_B(K) \
-  do { if (epilogue == CGAN_DTF_EPI_BUCKETIZE) DEC_NS(K, true); else DEC_NS(K, false); } while (0)
-    if (src_kind == CGAN_DTF_SRC_UNITY_D) DEC_B(CGAN_DTF_SRC_UNITY_D);
-    else if (src_kind == CGAN_DTF_SRC_KITTI_D) DEC_B(CGAN_DTF_SRC_KITTI_D);
-    else if (src_kind == CGAN_DTF_SRC_F32_D) DEC_B(CGAN_DTF_SRC_F32_D);
-    else if (src_kind == CGAN_DTF_SRC_MASK) DEC_NS(CGAN_DTF_SRC_MASK, false);
-    else if (src_kind == CGAN_DTF_SRC_SEG_EXACT) DEC_NS(CGAN_DTF_SRC_SEG_EXACT, false);
-    else if (src_kind == CGAN_DTF_SRC_SEG_NEAREST) DEC_NS(CGAN_DTF_SRC_SEG_NEAREST, false);
-    else if (epilogue == CGAN_DTF_EPI_BUCKETIZE) NEAR_NS(uint32_t, true);
-    else if (src_kind == CGAN_DTF_SRC_B8) NEAR_NS(uint64_t, false);
-    else NEAR_NS(uint32_t, false);
-#undef DEC_B
-#undef DEC_NS
-#undef DEC
-#undef NEAR_NS
-#undef NEAR
+    static_int<CGAN_DTF_SRC_SEG_NEAREST + 1>(src_kind, [&](auto K) {
+      static_int<3>(ns, [&](auto NS) {
+        static_int<2>(epilogue == CGAN_DTF_EPI_BUCKETIZE, [&](auto B) {
+          constexpr int kind = decltype(K)::value;
+          constexpr bool bucket = decltype(B)::value;
+          // uint8 is the bilinear mode's; only fp32 values bucketize: the 4-byte gather and the raw depths (checked above)
+          constexpr bool depth = kind == CGAN_DTF_SRC_UNITY_D || kind == CGAN_DTF_SRC_KITTI_D || kind == CGAN_DTF_SRC_F32_D;
+          if constexpr (kind != CGAN_DTF_SRC_U8 && (!bucket || kind == CGAN_DTF_SRC_B4 || depth))
+            hipLaunchKernelGGL((data_tf_nearest_kernel<kind, decltype(NS)::value, bucket>), grid, dim3(256), 0, s, items_device,
+                               boundaries, n_boundaries, pal);
+        });
+      });
+    });
   } else {
     const dim3 grid((unsigned)((max_pix + 255) / 256), count);
-#define BIL(U, NS, N) hipLaunchKernelGGL((data_tf_bilinear_kernel<U, NS, N>), grid, dim3(256), 0, s, items_device, aff)
-#define BIL_NS(U, N) \
-  do { if (ns == 0) BIL(U, 0, N); else if (ns == 1) BIL(U, 1, N); else BIL(U, 2, N); } while (0)
-    const bool norm = epilogue == CGAN_DTF_EPI_NORMALIZE;
-    if (src_kind == CGAN_DTF_SRC_U8) {
-      if (norm) BIL_NS(true, true); else BIL_NS(true, false);
-    } else {
-      if (norm) BIL_NS(false, true); else BIL_NS(false, false);
-    }
-#undef BIL_NS
-#undef BIL
+    static_int<2>(src_kind == CGAN_DTF_SRC_U8, [&](auto U) {
+      static_int<3>(ns, [&](auto NS) {
+        static_int<2>(epilogue == CGAN_DTF_EPI_NORMALIZE, [&](auto N) {
+          hipLaunchKernelGGL((data_tf_bilinear_kernel<decltype(U)::value != 0, decltype(NS)::value, decltype(N)::value != 0>),
+                             grid, dim3(256), 0, s, items_device, aff);
+        });
+      });
+    });
   }
   CGAN_CHECK_LAUNCH("data_transform");
   return CGAN_OK;

@@ -4,6 +4,7 @@ PyTorch is used only as the device-memory container / stream provider (tensor.da
 torch.cuda.current_stream()).  Every op here runs a hand-written HIP kernel from libcgan_hip.so; there is no
 torch fallback.
 """
+import collections
 import ctypes as C
 import functools
 import inspect
@@ -1718,8 +1719,24 @@ DTF_SRC_B4, DTF_SRC_B8, DTF_SRC_U8 = 0, 1, 2
 # raw sources of the nearest mode (include/climategan_hip.h): decoded per gathered pixel
 DTF_SRC_UNITY_D, DTF_SRC_KITTI_D, DTF_SRC_F32_D, DTF_SRC_MASK, DTF_SRC_SEG_EXACT, DTF_SRC_SEG_NEAREST = 3, 4, 5, 6, 7, 8
 DTF_DEC_LOG, DTF_DEC_NORMALIZE, DTF_DEC_THRESHOLD = 1, 2, 4
-_RAW_DTYPES = {DTF_SRC_UNITY_D: "uint8", DTF_SRC_KITTI_D: "uint16", DTF_SRC_F32_D: "float32", DTF_SRC_MASK: "uint8",
-               DTF_SRC_SEG_EXACT: "uint8", DTF_SRC_SEG_NEAREST: "uint8", DTF_SRC_U8: "uint8"}
+
+# An array as the image decoder leaves it (``transforms.RawSource`` says what each kind decodes to): the DTF_SRC_* code, the
+# task it belongs to, the array's dtype and numbers of dimensions, and its channel counts (None: any, or no channels)
+RawKind = collections.namedtuple("RawKind", "code task dtype dims chans")
+RAW_KINDS = {
+    "unity_d": RawKind(DTF_SRC_UNITY_D, "d", "uint8", (3,), (3, 4)),
+    "kitti_d": RawKind(DTF_SRC_KITTI_D, "d", "uint16", (2,), None),
+    "f32_d": RawKind(DTF_SRC_F32_D, "d", "float32", (2,), None),
+    "mask": RawKind(DTF_SRC_MASK, "m", "uint8", (2, 3), None),
+    "kitti_s": RawKind(DTF_SRC_SEG_EXACT, "s", "uint8", (3,), (3,)),
+    "palette_s": RawKind(DTF_SRC_SEG_NEAREST, "s", "uint8", (3,), (4,)),
+    "x": RawKind(DTF_SRC_U8, "x", "uint8", (3,), (3, 4)),
+}
+_RAW_BY_CODE = {k.code: k for k in RAW_KINDS.values()}
+_DEPTH_KINDS = (DTF_SRC_UNITY_D, DTF_SRC_KITTI_D, DTF_SRC_F32_D)
+# One sample's decode constants for ``data_transform(kind=...)``: the DTF_DEC_* bits, the Unity far plane, and the
+# whole-source (min, max - min) where the caller knows it (None: not needed, or read from ``stats``)
+DataDecode = collections.namedtuple("DataDecode", "flags far range", defaults=(0, 0.0, None))
 JIT_BRIGHTNESS, JIT_SATURATION, JIT_CONTRAST = 1, 2, 3
 
 
@@ -1737,8 +1754,19 @@ def _i32(what, *values):
 
 
 def raw_dtype(kind):
-    """The torch dtype of a raw source of ``kind``"""
-    return getattr(torch, _RAW_DTYPES[kind])
+    """The torch dtype of a raw source of ``kind`` (a DTF_SRC_* code)"""
+    return getattr(torch, _RAW_BY_CODE[kind].dtype)
+
+
+def _raw_arrays(what, sources, kind):
+    """The raw arrays of one launch: the dtype of ``kind``, [H, W] or [H, W, C], on one device"""
+    if kind not in _RAW_BY_CODE:
+        raise RuntimeError("%s: %d is no raw source kind" % (what, kind))
+    want, dev = raw_dtype(kind), sources[0].device
+    for t in sources:
+        if t.dtype != want or t.dim() not in (2, 3) or t.device != dev:
+            raise RuntimeError("%s: source kind %d reads %s [H, W] or [H, W, C] arrays, got %s %s"
+                               % (what, kind, want, tuple(t.shape), t.dtype))
 
 
 def data_palette(colours, classes, default_class=0):
@@ -1772,15 +1800,12 @@ def data_source_minmax(sources, kind: int, far=None) -> torch.Tensor:
     ``sources``: contiguous raw arrays of ``kind`` ([H, W] or [H, W, C]); ``far``: the Unity far plane per sample."""
     _need_cuda(*sources)
     n = len(sources)
-    want = raw_dtype(kind)
+    _raw_arrays("data_source_minmax", sources, kind)
     items = (_lib.DataMinmaxItem * n)()
     dev = sources[0].device
     out = torch.empty((n, 4), dtype=torch.float32, device=dev)
     keep = []
     for k, t in enumerate(sources):
-        if t.dtype != want or t.dim() not in (2, 3) or t.device != dev:
-            raise RuntimeError("data_source_minmax: source kind %d reads %s [H, W] or [H, W, C] arrays, got %s %s"
-                               % (kind, want, tuple(t.shape), t.dtype))
         if not t.is_contiguous() or t.data_ptr() % 16:
             t = t.clone(memory_format=torch.contiguous_format)
             keep.append(t)
@@ -1795,86 +1820,83 @@ def data_source_minmax(sources, kind: int, far=None) -> torch.Tensor:
     return out
 
 
-def data_transform(sources, plans, mode: int, normalize=None, boundaries: Optional[torch.Tensor] = None, u8_ranges=None,
-                   dense=True, raw=None, stats: Optional[torch.Tensor] = None):
+def _source_layout(t, raw):
+    """(h, w, c) and the element strides (stride_h, stride_w, stride_c) of one source: a raw [H, W] / [H, W, C] array, or a
+    [C, H, W] / [1, C, H, W] tensor"""
+    if raw:
+        (h, w), (sh, sw) = t.shape[:2], t.stride()[:2]
+        c, sc = (t.shape[2], t.stride(2)) if t.dim() == 3 else (1, 0)
+        return (h, w, c), (sh, sw, sc)
+    if t.dim() == 4 and t.shape[0] != 1:
+        raise RuntimeError("data_transform: a source is one sample ([1, C, H, W]), got %s" % (tuple(t.shape),))
+    if t.dim() not in (3, 4):
+        raise RuntimeError("data_transform: a source is [1, C, H, W] or [C, H, W], got %s" % (tuple(t.shape),))
+    (c, h, w), (sc, sh, sw) = t.shape[-3:], t.stride()[-3:]
+    return (h, w, c), (sh, sw, sc)
+
+
+def data_transform(sources, plans, mode: int, normalize=None, boundaries: Optional[torch.Tensor] = None, dense=True,
+                   kind: Optional[int] = None, decode=None, palette=None, stats: Optional[torch.Tensor] = None):
     """One launch: sample k's source map through its plan into its own [C, h, w] map (cgan_data_transform).
 
     ``sources``: device tensors, [1, C, H, W] or [C, H, W] with any strides (views are read in place), all fp32, all int32 or
-    all int64; or, with ``u8_ranges`` = [(min, max - min), ...], uint8 [H, W, C] images (bilinear only).  ``plans``: per
-    sample ``(stages, maps, (out_h, out_w))`` with ``stages`` up to two ``(in_h, in_w, out_h, out_w)`` and ``maps`` =
-    len(stages) + 1 triples ``(row_off, col_off, flip)`` (include/climategan_hip.h).  ``normalize`` = (mean, std) per channel
-    (bilinear), ``boundaries`` = the fp32 device tensor of torch.bucketize's boundaries (nearest, fp32 in, int32 out).
+    all int64 (``kind`` None: 4- or 8-byte elements by the dtype); or, with ``kind`` = a DTF_SRC_* code, the arrays as the
+    image decoder left them ([H, W] or [H, W, C] of the kind's dtype, ``RAW_KINDS``).  ``plans``: per sample ``(stages, maps,
+    (out_h, out_w))`` with ``stages`` up to two ``(in_h, in_w, out_h, out_w)`` and ``maps`` = len(stages) + 1 triples
+    ``(row_off, col_off, flip)`` (include/climategan_hip.h).  ``normalize`` = (mean, std) per channel (bilinear),
+    ``boundaries`` = the fp32 device tensor of torch.bucketize's boundaries (nearest, fp32 in, int32 out).
     Returns the dense [N, C, h, w] batch, or with ``dense=False`` a list of [1, C, h_k, w_k] maps (sizes may differ).
 
-    Raw sources (nearest mode): ``raw`` = dict(kind=DTF_SRC_*, flags=[DTF_DEC_* bits per sample], far=[far plane per sample]
-    or None, ranges=[(min, range) per sample] or None, palette=``data_palette(...)`` or None) and ``sources`` the arrays as
-    the image decoder left them ([H, W] or [H, W, C] of the kind's dtype); the decode runs on the gathered pixels and the
-    output has one channel (float64 for DTF_SRC_SEG_EXACT, else fp32; int32 with ``boundaries``).  ``stats``: the [N, 4]
-    tensor of ``data_source_minmax`` -- min, range and the mask's threshold flag then come from the device (raw sources, and
-    uint8 ``x`` images, for which ``u8_ranges`` is then None)."""
+    With a ``kind``, ``decode`` = one ``DataDecode`` per sample and ``palette`` = ``data_palette(...)`` for the segmentation
+    kinds.  DTF_SRC_U8 images go through the bilinear mode as ((float)v - min) / range per channel; every other kind through
+    the nearest mode, decoded on the gathered pixels into one channel (float64 for DTF_SRC_SEG_EXACT, else fp32; int32 with
+    ``boundaries``).  ``stats``: the [N, 4] tensor of ``data_source_minmax`` -- min, range and the mask's threshold flag then
+    come from the device."""
     _need_cuda(*sources, boundaries, stats)
     n = len(sources)
     if n == 0 or len(plans) != n:
         raise RuntimeError("data_transform: %d sources, %d plans" % (n, len(plans)))
     dt = sources[0].dtype
-    if any(t.dtype != dt or t.device != sources[0].device for t in sources):
-        raise RuntimeError("data_transform: the sources of one launch share dtype and device")
-    u8 = u8_ranges is not None or (stats is not None and raw is None)
     if stats is not None and (stats.dtype != torch.float32 or tuple(stats.shape) != (n, 4) or not stats.is_contiguous()):
         raise RuntimeError("data_transform: stats must be the contiguous [%d, 4] float32 tensor of data_source_minmax" % n)
-    if raw is not None:
-        kind = int(raw["kind"])
-        if kind not in _RAW_DTYPES or kind == DTF_SRC_U8:
-            raise RuntimeError("data_transform: %d is no raw source kind" % kind)
-        if u8_ranges is not None or normalize is not None or mode != DTF_NEAREST:
-            raise RuntimeError("data_transform: raw sources are read by the nearest mode, without u8_ranges or normalize")
-        if dt != raw_dtype(kind) or any(t.dim() not in (2, 3) for t in sources):
-            raise RuntimeError("data_transform: source kind %d reads %s [H, W] or [H, W, C] arrays, got %s"
-                               % (kind, raw_dtype(kind), dt))
-        if len(raw["flags"]) != n:
-            raise RuntimeError("data_transform: %d sources, %d decode flags" % (n, len(raw["flags"])))
-        if boundaries is not None and kind not in (DTF_SRC_UNITY_D, DTF_SRC_KITTI_D, DTF_SRC_F32_D):
+    raw = kind is not None
+    if raw:
+        kind = int(kind)
+        _raw_arrays("data_transform", sources, kind)
+        if kind == DTF_SRC_U8 and (mode != DTF_BILINEAR or any(t.dim() != 3 for t in sources)):
+            raise RuntimeError("data_transform: uint8 images are [H, W, C] sources of the bilinear mode")
+        if kind != DTF_SRC_U8 and (normalize is not None or mode != DTF_NEAREST):
+            raise RuntimeError("data_transform: raw sources are read by the nearest mode, without normalize")
+        if decode is None or len(decode) != n:
+            raise RuntimeError("data_transform: %d sources, %s decode records" % (n, "no" if decode is None else len(decode)))
+        if boundaries is not None and kind not in _DEPTH_KINDS:
             raise RuntimeError("data_transform: bucketize reads depth sources")
-    elif u8:
-        if dt != torch.uint8 or mode != DTF_BILINEAR or any(t.dim() != 3 for t in sources):
-            raise RuntimeError("data_transform: u8_ranges go with uint8 [H, W, C] sources in the bilinear mode")
-        kind = 2
+    elif decode is not None or palette is not None or stats is not None:
+        raise RuntimeError("data_transform: decode records, a palette and stats go with a source kind")
+    elif any(t.dtype != dt or t.device != sources[0].device for t in sources):
+        raise RuntimeError("data_transform: the sources of one launch share dtype and device")
     elif dt in (torch.float32, torch.int32):
-        kind = 0
+        kind = DTF_SRC_B4
     elif dt in (torch.int64, torch.float64):   # float64: the kitti segmentation map of process_kitti_seg
-        kind = 1
+        kind = DTF_SRC_B8
     else:
-        raise RuntimeError("data_transform: sources must be float32, int32, int64, float64 or (with u8_ranges) uint8, got %s"
-                           % dt)
-    if (mode == DTF_BILINEAR or boundaries is not None) and not u8 and raw is None and dt != torch.float32:
+        raise RuntimeError("data_transform: sources must be float32, int32, int64 or float64 tensors, or raw arrays with "
+                           "their kind, got %s" % dt)
+    if (mode == DTF_BILINEAR or boundaries is not None) and not raw and dt != torch.float32:
         raise RuntimeError("data_transform: the bilinear mode and bucketize read float32 maps, got %s" % dt)
     epi = DTF_EPI_NONE
     mean = std = None
     if normalize is not None:
         epi, mean, std = DTF_EPI_NORMALIZE, _f4(normalize[0]), _f4(normalize[1])
+    out_dt = dt if mode == DTF_NEAREST and not raw else (torch.float64 if kind == DTF_SRC_SEG_EXACT else torch.float32)
     if boundaries is not None:
         if boundaries.dtype != torch.float32 or boundaries.dim() != 1 or not boundaries.is_contiguous():
             raise RuntimeError("data_transform: boundaries must be a contiguous 1-D float32 tensor")
-        epi = DTF_EPI_BUCKETIZE
-    out_dt = torch.int32 if boundaries is not None else (torch.float32 if mode == DTF_BILINEAR else dt)
-    if raw is not None and boundaries is None:
-        out_dt = torch.float64 if kind == DTF_SRC_SEG_EXACT else torch.float32
+        epi, out_dt = DTF_EPI_BUCKETIZE, torch.int32
     items = (_lib.DataTfItem * n)()
     shapes, total = [], 0
     for k, (t, (stages, maps, (oh, ow))) in enumerate(zip(sources, plans)):
-        if raw is not None:
-            (h, w), (sh, sw) = t.shape[:2], t.stride()[:2]
-            c, sc = (t.shape[2], t.stride(2)) if t.dim() == 3 else (1, 0)
-        elif u8:
-            (h, w, c), (sh, sw, sc) = t.shape, t.stride()
-        else:
-            if t.dim() == 4:
-                if t.shape[0] != 1:
-                    raise RuntimeError("data_transform: a source is one sample ([1, C, H, W]), got %s" % (tuple(t.shape),))
-                t = t[0]
-            if t.dim() != 3:
-                raise RuntimeError("data_transform: a source is [1, C, H, W] or [C, H, W], got %s" % (tuple(t.shape),))
-            (c, h, w), (sc, sh, sw) = t.shape, t.stride()
+        (h, w, c), (sh, sw, sc) = _source_layout(t, raw)
         if len(stages) > 2 or len(maps) != len(stages) + 1:
             raise RuntimeError("data_transform: a plan has at most two stages and one map more than stages")
         it = items[k]
@@ -1883,14 +1905,12 @@ def data_transform(sources, plans, mode: int, normalize=None, boundaries: Option
         it.stride_c, it.stride_h, it.stride_w = _i32("source stride", sc, sh, sw)
         it.out_h, it.out_w = _i32("output size", oh, ow)
         it.n_stages = len(stages)
-        if u8_ranges is not None:
-            it.u8_min, it.u8_range = float(u8_ranges[k][0]), float(u8_ranges[k][1])
-        if raw is not None:
-            it.dec_flags = int(raw["flags"][k])
-            it.far_plane = float(raw["far"][k]) if raw.get("far") is not None else 0.0
-            if raw.get("ranges") is not None and raw["ranges"][k] is not None:
-                it.u8_min, it.u8_range = float(raw["ranges"][k][0]), float(raw["ranges"][k][1])
-            c = 1                                   # the decoded map has one channel
+        if raw:
+            it.dec_flags, it.far_plane = int(decode[k].flags), float(decode[k].far)
+            if decode[k].range is not None:
+                it.u8_min, it.u8_range = float(decode[k].range[0]), float(decode[k].range[1])
+            if kind != DTF_SRC_U8:
+                c = 1                               # the decoded map has one channel
         if stats is not None:
             it.stats = stats[k].data_ptr()
         for i, st in enumerate(stages):
@@ -1912,8 +1932,7 @@ def data_transform(sources, plans, mode: int, normalize=None, boundaries: Option
         items[k].dst = flat.data_ptr() + off * flat.element_size()
         off += c * oh * ow
     table = _item_table(items, dev)
-    palette = raw.get("palette") if raw is not None else None
-    _lib.check(_lib.load().cgan_data_transform_raw(
+    _lib.check(_lib.load().cgan_data_transform(
         C.cast(items, C.c_void_p), C.c_void_p(table.data_ptr()), n, int(mode), kind, epi,
         C.cast(mean, C.c_void_p) if mean is not None else None, C.cast(std, C.c_void_p) if std is not None else None,
         _ptr(boundaries), 0 if boundaries is None else boundaries.numel(),

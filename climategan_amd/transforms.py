@@ -312,34 +312,9 @@ class Plan:
             lo = hi
 
 
-class U8Image:
-    """An ``x`` source as the decoder left it: a uint8 [H, W, 3] device tensor and the image's ``min`` and ``max``.  The
-    kernels apply ``tensor_loader``'s ``arr -= arr.min(); arr /= arr.max()`` (data.py:385-387) on the fly as
-    ``((float)v - min) / (max - min)``: a quarter of the upload of the fp32 tensor, the same bits."""
-
-    def __init__(self, hwc, vmin, vmax):
-        if hwc.dtype != torch.uint8 or hwc.dim() != 3:
-            raise RuntimeError("U8Image: a uint8 [H, W, C] tensor, got %s %s" % (tuple(hwc.shape), hwc.dtype))
-        self.t, self.min, self.range = hwc, float(vmin), float(vmax) - float(vmin)
-
-    @classmethod
-    def from_numpy(cls, arr, device):
-        return cls(torch.from_numpy(np.ascontiguousarray(arr)).to(device), arr.min(), arr.max())
-
-    @property
-    def shape(self):
-        h, w, c = self.t.shape
-        return (1, c, h, w)
-
-    def to_float(self):
-        """``tensor_loader``'s fp32 [1, 3, H, W] tensor (one launch)"""
-        _, _, h, w = self.shape
-        return _run_one(self.t, Plan(h, w), ops.DTF_BILINEAR, u8_ranges=[(self.min, self.range)])
-
-
 class RawSource:
     """A ``d``, ``m``, ``s`` or ``x`` source as the image decoder left it: the raw device array and what it encodes.  The
-    gather decodes the pixels it reads (``ops.data_transform(raw=...)``, csrc/data_tf.hip), so nothing passes over the whole
+    gather decodes the pixels it reads (``ops.data_transform(kind=...)``, csrc/data_tf.hip), so nothing passes over the whole
     source on the host; the one thing that has to see every pixel -- the min / max of a normalised depth, of ``x``, and the
     mask's "max > 127" -- is two launches on the raw bytes (``ops.data_source_minmax``) unless the caller knows it.
 
@@ -351,31 +326,24 @@ class RawSource:
                    ``threshold`` = that flag when the caller knows it
       "kitti_s"    uint8 [H, W, 3]: ``process_kitti_seg`` (data.py:129-148), float64 class ids
       "palette_s"  uint8 [H, W, 4] RGBA: ``encode_segmap`` (data.py:231-252) for ``domain`` "s" or "r", fp32 class ids
-      "x"          uint8 [H, W, 3 or 4]: ``arr -= arr.min(); arr /= arr.max()`` (data.py:385-387); a ``U8Image`` whose min
-                   and max are found on the device
+      "x"          uint8 [H, W, 3 or 4]: ``arr -= arr.min(); arr /= arr.max()`` (data.py:385-387), read by the bilinear mode
+                   as ``((float)v - min) / (max - min)``: a quarter of the upload of the fp32 tensor, the same bits
     ``minmax`` = the known (min, max) of the decoded map (of the raw bytes for "x").  A fourth channel of "x" and "mask" is
-    dropped first, as tensor_loader does (data.py:382-383)."""
-
-    KINDS = {"unity_d": ops.DTF_SRC_UNITY_D, "kitti_d": ops.DTF_SRC_KITTI_D, "f32_d": ops.DTF_SRC_F32_D,
-             "mask": ops.DTF_SRC_MASK, "kitti_s": ops.DTF_SRC_SEG_EXACT, "palette_s": ops.DTF_SRC_SEG_NEAREST,
-             "x": ops.DTF_SRC_U8}
-    TASKS = {"unity_d": "d", "kitti_d": "d", "f32_d": "d", "mask": "m", "kitti_s": "s", "palette_s": "s", "x": "x"}
+    dropped first, as tensor_loader does (data.py:382-383).  Dtype, dimensions and channel counts: ``ops.RAW_KINDS``."""
 
     def __init__(self, arr, kind, far=1000, log=False, normalize=False, minmax=None, threshold=None, palette=None):
-        if kind not in self.KINDS:
-            raise ValueError("RawSource: kind %r; one of %s" % (kind, sorted(self.KINDS)))
+        if kind not in ops.RAW_KINDS:
+            raise ValueError("RawSource: kind %r; one of %s" % (kind, sorted(ops.RAW_KINDS)))
         assert not (normalize and log)                                          # tutils.py:196
-        code = self.KINDS[kind]
-        dims = {"unity_d": (3,), "kitti_d": (2,), "f32_d": (2,), "mask": (2, 3), "kitti_s": (3,), "palette_s": (3,), "x": (3,)}
-        if arr.dtype != ops.raw_dtype(code) or arr.dim() not in dims[kind]:
+        code, self.task, _, dims, chans = ops.RAW_KINDS[kind]
+        if arr.dtype != ops.raw_dtype(code) or arr.dim() not in dims:
             raise RuntimeError("RawSource: %r is a %s array of %s dimensions, got %s %s"
-                               % (kind, ops.raw_dtype(code), " or ".join(map(str, dims[kind])), tuple(arr.shape), arr.dtype))
-        chans = {"unity_d": (3, 4), "kitti_s": (3,), "palette_s": (4,), "x": (3, 4)}
-        if kind in chans and arr.shape[2] not in chans[kind]:
-            raise RuntimeError("RawSource: %r has %s channels, got %d" % (kind, " or ".join(map(str, chans[kind])), arr.shape[2]))
+                               % (kind, ops.raw_dtype(code), " or ".join(map(str, dims)), tuple(arr.shape), arr.dtype))
+        if chans is not None and arr.shape[2] not in chans:
+            raise RuntimeError("RawSource: %r has %s channels, got %d" % (kind, " or ".join(map(str, chans)), arr.shape[2]))
         if kind in ("x", "mask") and arr.dim() == 3 and arr.shape[2] == 4:
             arr = arr[:, :, :3]
-        if kind in ("kitti_s", "palette_s") and palette is None:
+        if self.task == "s" and palette is None:
             raise ValueError("RawSource: %r needs its palette (climategan_amd.data builds it)" % kind)
         self.t, self.kind, self.code, self.palette = arr, kind, code, palette
         self.far, self.log = float(far), bool(log)
@@ -400,10 +368,6 @@ class RawSource:
         return cls(torch.from_numpy(np.ascontiguousarray(arr)).to(device), kind, **kw)
 
     @property
-    def task(self):
-        return self.TASKS[self.kind]
-
-    @property
     def shape(self):
         return (1, 3 if self.kind == "x" else 1, int(self.t.shape[0]), int(self.t.shape[1]))
 
@@ -420,6 +384,11 @@ class RawSource:
     def flags(self):
         return ((ops.DTF_DEC_LOG if self.log else 0) | (ops.DTF_DEC_NORMALIZE if self.normalize and self.kind != "f32_d" else 0)
                 | (ops.DTF_DEC_THRESHOLD if self.threshold else 0))
+
+    @property
+    def decode(self):
+        """This sample's record for ``ops.data_transform(kind=...)``"""
+        return ops.DataDecode(self.flags, self.far, None if self.min is None else (self.min, self.range))
 
     def to_tensor(self):
         """``tensor_loader``'s [1, C, H, W] tensor: the identity plan through the same kernel"""
@@ -438,12 +407,8 @@ def _run_raw(sources, plans, dense=True, **kw):
     stats = None
     if any(s.needs_stats for s in sources):
         stats = ops.data_source_minmax(arrays, first.code, far=[s.far for s in sources])
-    if first.kind == "x":
-        ranges = None if stats is not None else [(s.min, s.range) for s in sources]
-        return ops.data_transform(arrays, plans, ops.DTF_BILINEAR, u8_ranges=ranges, stats=stats, dense=dense, **kw)
-    raw = dict(kind=first.code, flags=[s.flags for s in sources], far=[s.far for s in sources], palette=first.palette,
-               ranges=[(s.min, s.range) if s.min is not None else None for s in sources])
-    return ops.data_transform(arrays, plans, ops.DTF_NEAREST, raw=raw, stats=stats, dense=dense, **kw)
+    return ops.data_transform(arrays, plans, _mode(first.task), kind=first.code, decode=[s.decode for s in sources],
+                              palette=first.palette, stats=stats, dense=dense, **kw)
 
 
 def _hw(v):
@@ -465,11 +430,8 @@ def _pair(size, what):
 
 
 def _tensors_only(data, who):
-    """The per-sample classes read device tensors; a ``U8Image`` belongs to the batch form (or ``to_float()`` first)"""
+    """The per-sample classes read device tensors; a ``RawSource`` belongs to the batch form (or ``to_tensor()`` first)"""
     for task, v in data.items():
-        if isinstance(v, U8Image):
-            raise TypeError("%s: %r is a U8Image; the per-sample transforms take tensors -- call .to_float() first, or use "
-                            "compile_transforms, which reads the uint8 image directly" % (who, task))
         if isinstance(v, RawSource):
             raise TypeError("%s: %r is a RawSource; the per-sample transforms take tensors -- call .to_tensor() first, or use "
                             "compile_transforms, which reads the raw array directly" % (who, task))
@@ -728,10 +690,11 @@ class Compose:
 
 class BatchTransform:
     """The transform list of ``get_transforms`` on a whole batch: ``batch(samples)`` with ``samples`` a list of N dicts
-    ``{task: [1, C, H, W] device tensor}`` (``x`` may be a ``U8Image``, any task a ``RawSource`` of its kind) returns ``{task: [N, C, h, w]}``, the reference's
-    collated batch.  Per sample it makes the reference's draws in the reference's order and reduces every task's flips,
-    crops and resizes to a ``Plan`` on the host; then each task is ONE launch for the whole batch (one more per two further
-    resizes beyond the second), plus one launch per colour-jitter item on ``x`` (two for contrast: its mean)."""
+    ``{task: [1, C, H, W] device tensor}`` (or, for every sample of a task, a ``RawSource`` of its kind) returns
+    ``{task: [N, C, h, w]}``, the reference's collated batch.  Per sample it makes the reference's draws in the reference's
+    order and reduces every task's flips, crops and resizes to a ``Plan`` on the host; then each task is ONE launch for the
+    whole batch (one more per two further resizes beyond the second), plus one launch per colour-jitter item on ``x`` (two
+    for contrast: its mean)."""
 
     def __init__(self, transforms, draws=None):
         self.transforms = list(transforms)
@@ -782,18 +745,10 @@ class BatchTransform:
         out = {}
         for task in tasks:
             sources = [s[task] for s in samples]
-            u8 = None
-            n_u8 = sum(isinstance(v, U8Image) for v in sources)
-            if n_u8 not in (0, len(sources)) or (n_u8 and task != "x"):
-                raise TypeError("BatchTransform: %r is a U8Image in %d of %d samples; one launch reads one kind of source "
-                                "(all uint8 images, x only, or all tensors)" % (task, n_u8, len(sources)))
             n_raw = sum(isinstance(v, RawSource) for v in sources)
             if n_raw not in (0, len(sources)) or any(isinstance(v, RawSource) and v.task != task for v in sources):
                 raise TypeError("BatchTransform: %r is a RawSource in %d of %d samples, or of another task's kind; one "
                                 "launch reads one kind of source" % (task, n_raw, len(sources)))
-            if n_u8:
-                u8 = [(s.min, s.range) for s in sources]
-                sources = [s.t for s in sources]
             chunks = [p[task].launches() for p, _ in planned]
             mode = _mode(task)
             for i in range(len(chunks[0])):
@@ -806,8 +761,7 @@ class BatchTransform:
                 if n_raw and i == 0:        # the decode belongs to the launch that reads the source
                     sources = _run_raw(sources, [c[i] for c in chunks], dense=last, **kw)
                 else:
-                    sources = ops.data_transform(sources, [c[i] for c in chunks], mode, u8_ranges=u8, dense=last, **kw)
-                u8 = None
+                    sources = ops.data_transform(sources, [c[i] for c in chunks], mode, dense=last, **kw)
             y = sources
             if task == "x":
                 for k, t in enumerate(jitter):

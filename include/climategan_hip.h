@@ -983,10 +983,6 @@ typedef struct {
   uint32_t colour[16];
   int32_t cls[16];
 } CganDataTfPalette;
-/* cgan_data_transform with the raw source kinds: the same call plus the palette (NULL unless a SEG kind). */
-int cgan_data_transform_raw(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count, int32_t mode,
-                            int32_t src_kind, int32_t epilogue, const float* mean, const float* std, const float* boundaries,
-                            int32_t n_boundaries, const CganDataTfPalette* palette, void* stream);
 /* Whole-source min / max of `count` samples in two launches (fixed-range partials, then a fixed-order finish; no atomics, no
  * host synchronisation): out[0] = min, out[1] = max - min in fp32, out[2] = max, out[3] = max > 127 ? 1 : 0, of
  *   CGAN_DTF_SRC_U8 / MASK  every byte of the array as a float (tensor_loader's arr.min() / arr.max(), all channels)
@@ -1002,9 +998,10 @@ typedef struct {
 } CganDataMinmaxItem;
 int cgan_data_source_minmax(const CganDataMinmaxItem* items_host, const CganDataMinmaxItem* items_device, int32_t count,
                             int32_t src_kind, float* ws, void* stream);
+/* palette: NULL unless src_kind is a SEG kind */
 int cgan_data_transform(const CganDataTfItem* items_host, const CganDataTfItem* items_device, int32_t count, int32_t mode,
                         int32_t src_kind, int32_t epilogue, const float* mean, const float* std, const float* boundaries,
-                        int32_t n_boundaries, void* stream);
+                        int32_t n_boundaries, const CganDataTfPalette* palette, void* stream);
 int cgan_data_jitter(const float* x, float* y, const float* factors, int32_t op, int32_t n, int32_t h, int32_t w,
                      const float* mean, const float* std, float* ws, void* stream);
 

@@ -209,7 +209,7 @@ def _item(kind, **kw):
 def _call(items, kind, mode=ops.DTF_NEAREST, epi=ops.DTF_EPI_NONE, palette=None):
     p = C.cast(items, C.c_void_p)
     pal = C.cast(C.pointer(palette), C.c_void_p) if palette is not None else None
-    return _lib.load().cgan_data_transform_raw(p, p, 1, mode, kind, epi, None, None, None, 0, pal, None)
+    return _lib.load().cgan_data_transform(p, p, 1, mode, kind, epi, None, None, None, 0, pal, None)
 
 
 @pytest.mark.parametrize("what, items, kw", [

@@ -121,7 +121,8 @@ def test_known_constants_equal_the_device_ones():
     m = cases.mask("known.m", 255)
     assert torch.equal(T.RawSource.from_numpy(m, "mask", DEV).to_tensor(), T.RawSource.from_numpy(m, "mask", DEV, threshold=True).to_tensor())
     x = cases.x_image("known.x")
-    assert torch.equal(T.RawSource.from_numpy(x, "x", DEV).to_tensor(), T.U8Image.from_numpy(x, DEV).to_float())
+    assert torch.equal(T.RawSource.from_numpy(x, "x", DEV).to_tensor(),
+                       T.RawSource.from_numpy(x, "x", DEV, minmax=(x.min(), x.max())).to_tensor())
 
 
 def test_minmax_is_the_same_every_run_and_equals_torch():

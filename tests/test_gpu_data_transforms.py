@@ -13,6 +13,7 @@ import random
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 import data_transform_cases as dc
 from climategan_amd import fill
@@ -47,10 +48,50 @@ def x_bound(case):
     return 2e-6 / min(std)
 
 
-@pytest.mark.parametrize("name", list(dc.CASES))
+# The plain gather on its own: a multi-channel source read in place through a non-contiguous view, 4-byte (fp32) and 8-byte
+# (float64) elements, 0, 1 and 2 stages, flipped in every map or in none, a crop offset in every map; against CPU torch
+# applying torch.flip, slicing and F.interpolate(mode="nearest") in the same order.  33 x 47 = 1551 output pixels: one full
+# block of 1024 and one whose threads own 1 to 3 live pixels of their 4; 1 x 1: a single live pixel.
+PLAIN_GATHER = {"plain_gather_f32x3": (torch.float32, 3), "plain_gather_f64x2": (torch.float64, 2)}
+
+
+def plain_gather_equals_torch(name):
+    from climategan_amd import ops, transforms as T
+
+    dtype, c = PLAIN_GATHER[name]
+    if dtype == torch.float32:      # CHW inside a larger CHW tensor; every element distinct and exact
+        big, view = torch.arange(c * 56 * 80, dtype=dtype).reshape(c, 56, 80), lambda t: t[:, 3:53, 5:75]
+    else:                           # an HWC tensor seen as CHW: channel stride 1, column stride C
+        big, view = torch.arange(60 * 80 * c, dtype=dtype).reshape(60, 80, c), lambda t: t.permute(2, 0, 1)[:, 3:53, 5:75]
+    cpu, dev = view(big), view(big.to(DEV))
+    assert tuple(dev.shape) == (c, 50, 70) and not dev.is_contiguous()
+    for oh, ow in [(33, 47), (1, 1)]:
+        crops = [(2, 3, oh + 11, ow + 13), (1, 2, oh + 4, ow + 2), (2, 1, oh, ow)]
+        sizes = [(oh + 7, ow + 5), (oh + 3, ow + 3)]
+        for ns in (0, 1, 2):
+            for flip in (False, True):
+                plan, want = T.Plan(50, 70), cpu.unsqueeze(0)
+                for k, (top, left, h, w) in enumerate(crops[:ns] + crops[-1:]):
+                    if flip:
+                        plan.flip()
+                        want = torch.flip(want, [3])
+                    plan.crop(top, left, h, w)
+                    want = want[:, :, top:top + h, left:left + w]
+                    if k < ns:
+                        plan.resize(*sizes[2 - ns + k])
+                        want = F.interpolate(want, size=sizes[2 - ns + k], mode="nearest")
+                (launch,) = plan.launches()
+                assert len(launch[0]) == ns and all(m[0] and m[1] and m[2] == flip for m in launch[1])
+                got = ops.data_transform([dev], [launch], ops.DTF_NEAREST)
+                assert got.dtype == dtype and torch.equal(got.cpu(), want), (name, oh, ow, ns, flip)
+
+
+@pytest.mark.parametrize("name", list(dc.CASES) + list(PLAIN_GATHER))
 def test_case_equals_the_reference(name, golden):
     from climategan_amd import transforms as T
 
+    if name in PLAIN_GATHER:
+        return plain_gather_equals_torch(name)
     case = dc.CASES[name]
     samples = device_samples(name, case)
     draws = T.RecordedPipelineDraws(recorded(golden, name))
@@ -95,10 +136,10 @@ def test_uint8_sources_equal_the_fp32_path_bit_for_bit():
 
     case = dc.CASES["default_train"]
     imgs = [u8_image(90, 130, 1), u8_image(130, 90, 2), u8_image(77, 77, 3)]
-    u8 = [{"x": T.U8Image.from_numpy(a, DEV)} for a in imgs]
+    u8 = [{"x": T.RawSource.from_numpy(a, "x", DEV, minmax=(a.min(), a.max()))} for a in imgs]
     f32 = [{"x": tensor_loader_x(a).to(DEV)} for a in imgs]
     for a, b in zip(u8, f32):
-        assert torch.equal(a["x"].to_float(), b["x"])
+        assert torch.equal(a["x"].to_tensor(), b["x"])
     outs = []
     for samples in (u8, f32):
         dc.seed_all(5)
@@ -225,11 +266,12 @@ def test_pipeline_with_jitter():
 def test_u8_images_are_refused_where_they_cannot_go():
     from climategan_amd import transforms as T
 
-    img = T.U8Image.from_numpy(u8_image(20, 30, 1), DEV)
-    x = img.to_float()
+    arr = u8_image(20, 30, 1)
+    img = T.RawSource.from_numpy(arr, "x", DEV, minmax=(arr.min(), arr.max()))
+    x = img.to_tensor()
     for t in (T.Resize(8), T.RandomCrop(4, center=True), T.RandomHorizontalFlip(1.0), T.Normalize(dc.mirror_opts({"items": []})),
               T.RandBrightness()):
-        with pytest.raises(TypeError, match="to_float"):
+        with pytest.raises(TypeError, match="to_tensor"):
             t({"x": img})
     with pytest.raises(TypeError, match="1 of 2 samples"):
         T.BatchTransform([T.Resize(8)])([{"x": img}, {"x": x}])

@@ -21,6 +21,7 @@ and prints no timing.
 import argparse
 import json
 import math
+import random
 import statistics
 import sys
 import time
@@ -120,6 +121,8 @@ def main():
     ap.add_argument("--batches", default="1,4,32")
     ap.add_argument("--normalize", action="store_true", help="min-max normalise d (train.pseudo.tasks holds d)")
     args = ap.parse_args()
+    np.random.seed(0)       # the timed crops and flips come from the global generators: two builds time the same windows
+    random.seed(0)
     opts = Opts({"tasks": ["d", "s", "m", "p"], "data": {"transforms": ITEMS}})
     batch = T.compile_transforms(opts, "train", "s", draws=T.PipelineDraws())
     result = {"what": "decode + default loader transforms from raw sim-domain sources around 1200x1800, tasks d s m x",
