@@ -52,6 +52,19 @@ class PackItem(C.Structure):
                 ("kw", C.c_int32), ("transposed", C.c_int32)]
 
 
+class JpegHuffTab(C.Structure):
+    """cgan_jpeg_hufftab: a Huffman table in the decode form (climategan_hip.h)."""
+    _fields_ = [("limit", C.c_uint32 * 17), ("offset", C.c_int32 * 17), ("vals", C.c_uint8 * 256)]
+
+
+class JpegDesc(C.Structure):
+    """cgan_jpeg_desc: one baseline JPEG file as ``cgan_jpeg_parse_host`` describes it, plus the caller's two offsets."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+                ("restart_interval", C.c_int32), ("scan_offset", C.c_uint32), ("scan_bytes", C.c_uint32),
+                ("blob_offset", C.c_int64), ("out_offset", C.c_int64), ("quant", (C.c_uint8 * 64) * 3),
+                ("dc", JpegHuffTab * 3), ("ac", JpegHuffTab * 3)]
+
+
 class AdamItem(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("copy", C.c_void_p),
                 ("numel", C.c_int64)]
@@ -264,6 +277,12 @@ _SIGNATURES = {
     "cgan_jpeg_coefficients_u8": (C.c_int, [_P] + [C.c_int32] * 6 + [_P, _P]),
     "cgan_jpeg_tables": (C.c_int, [C.c_int32, _P, _P]),
     "cgan_jpeg_scan_host": (C.c_int, [_P] + [C.c_int32] * 5 + [_P, C.c_size_t, _P]),
+    "cgan_jpeg_parse_host": (C.c_int, [_P, C.c_size_t, _P, _P]),
+    "cgan_jpeg_decode_coefficients_host": (C.c_int, [_P, C.c_size_t, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
+    "cgan_jpeg_decode_workspace_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "cgan_jpeg_decode_u8": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "cgan_jpeg_decode_coefficients": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P,
+                                                C.c_size_t, _P]),
     "cgan_smog_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "cgan_smog_nchw": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), _P, C.c_size_t, _P]),

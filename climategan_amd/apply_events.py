@@ -15,7 +15,8 @@ message instead of the reference's ``input()`` prompt, which nobody answers in a
 written batch by batch rather than all held in memory; ``--dtype`` selects the kernels' 16-bit type; ``--png_level 2`` asks
 the device PNG encoder for smaller files (same pixels; neither is an option of the reference's script); ``--format jpg``
 writes the events and the input picture as baseline JPEG files from the device encoder (``jpeg.write``, DESIGN 4.19;
-``--jpeg_quality``, ``--jpeg_subsampling``) -- several times smaller, lossy; the masks stay PNG.
+``--jpeg_quality``, ``--jpeg_subsampling``) -- several times smaller, lossy; the masks stay PNG; ``--decode device`` uploads
+baseline JPEG inputs as file bytes and decodes them with the device decoder (``jpeg.decode``).
 """
 import argparse
 import shutil
@@ -88,16 +89,17 @@ EVENT_ORDER = ("flood", "wildfire", "smog", "mask", "input")       # the order i
 class _Args(argparse.Namespace):
     """``png_level`` is 1 unless the command line gives it: an attribute with a class default, so that the namespace of a
     run without it -- what ``main`` prints under "Using args" -- holds the entries it held before the option existed.  The
-    same for ``format`` and the two JPEG options."""
+    same for ``format``, the two JPEG options and ``decode``."""
     png_level = 1
+    decode = "host"
     format = "png"
     jpeg_quality = 90
     jpeg_subsampling = "444"
 
 
 def parse_args(argv=None):
-    """apply_events.py:4-148 (same names, short forms, defaults and help) + ``--dtype``, ``--png_level``, ``--format`` and
-    the two ``--jpeg_*`` options."""
+    """apply_events.py:4-148 (same names, short forms, defaults and help) + ``--dtype``, ``--png_level``, ``--format``, the
+    two ``--jpeg_*`` options and ``--decode``."""
     argv = list(sys.argv[1:] if argv is None else argv)
     for a in argv:
         key = a.split("=", 1)[0]
@@ -151,6 +153,10 @@ def parse_args(argv=None):
                         help="With --format jpg: libjpeg's quality scale, 1 to 100. Defaults to 90")
     parser.add_argument("--jpeg_subsampling", default=argparse.SUPPRESS, choices=("444", "420"),
                         help="With --format jpg: chroma at full resolution (444) or halved both ways (420). Defaults to 444")
+    parser.add_argument("--decode", default=argparse.SUPPRESS, choices=("host", "device"),
+                        help="Not an option of the reference's script: where the input files are decoded. device: baseline "
+                        "JPEG files are uploaded as bytes and decoded by the device decoder; every other file, and any the "
+                        "device reports as corrupt, is read on the host as with host. Defaults to host")
     args = parser.parse_args(argv, namespace=_Args())
     given = vars(args)
     if args.format != "jpg" and ("jpeg_quality" in given or "jpeg_subsampling" in given):
@@ -277,6 +283,24 @@ def read_image(path):
     return a if a.shape[2] == 3 else rgba_to_rgb(a)
 
 
+def read_images(paths, decode="host", device="cuda"):
+    """The batch's images, each uint8 [H, W, 3]: host arrays from ``read_image``, or with ``decode="device"`` device tensors
+    from ``jpeg.decode`` for the files ``jpeg.probe`` accepts as 3-component baseline JPEG.  Everything else --
+    PNG, progressive JPEG, a file the device reports as corrupt or not converged -- goes through ``read_image`` unchanged;
+    a grey JPEG is refused with ``read_image``'s message in both modes."""
+    if decode != "device":
+        return [read_image(p) for p in paths]
+    from . import jpeg
+
+    datas = [Path(p).read_bytes() for p in paths]
+    images = [None] * len(paths)
+    pick = [i for i, data in enumerate(datas) if getattr(jpeg.probe(data)[0], "ncomp", 0) == 3]
+    if pick:
+        for i, im in zip(pick, jpeg.try_decode([datas[i] for i in pick], device=device)[0]):
+            images[i] = im
+    return [read_image(p) if im is None else im for p, im in zip(paths, images)]
+
+
 def event_file_name(stem, event, width, keep_ratio, no_cloudy, ext="png"):
     """apply_events.py:590-616; ``ext``: "jpg" for the files ``--format jpg`` writes."""
     suffix = ("_AR" if keep_ratio else "") + ("_no_cloudy" if no_cloudy else "")
@@ -369,7 +393,7 @@ def main(argv=None):
         for b in range(0, len(data_paths), batch_size):
             paths = data_paths[b:b + batch_size]
             with timed("data pre-processing"):
-                images = [read_image(p) for p in paths]
+                images = read_images(paths, args.decode, trainer.device)
                 if keep_ratio:
                     x = torch.stack([resize_keep_ratio(im, max_im_width, device=trainer.device) for im in images])
                 else:

@@ -745,6 +745,48 @@ def jpeg_coefficients(img_u8: torch.Tensor, quality: int = 90, subsampling="444"
     return coef
 
 
+JPEG_DECODE_MAX_DIM = 8192   # the widest and the highest file cgan_jpeg_decode_u8 takes
+JPEG_OK, JPEG_UNSUPPORTED, JPEG_CORRUPT, JPEG_NOT_CONVERGED = 0, 1, 2, 4     # a file's status bits (climategan_hip.h)
+
+
+def jpeg_blocks(d) -> int:
+    """The 8 x 8 blocks of the file a ``_lib.JpegDesc`` describes: every component over the frame padded to whole MCUs."""
+    mx, my = -(-d.width // (8 * d.hs)), -(-d.height // (8 * d.vs))
+    return mx * my * (d.hs * d.vs + (2 if d.ncomp == 3 else 0))
+
+
+def jpeg_decode(blob: torch.Tensor, descs, descs_dev: torch.Tensor, subseq_bytes: int = 0, coefficients: bool = False):
+    """The device JPEG decoder.  ``blob``: uint8 device tensor with the files' bytes; ``descs``: a ctypes array
+    of ``_lib.JpegDesc`` as ``cgan_jpeg_parse_host`` filled them, ``blob_offset`` / ``out_offset`` set by the caller;
+    ``descs_dev``: the same bytes as a uint8 device tensor -> (out, status).  ``out``: one uint8 tensor, file i's [H, W, C]
+    pixels from ``out_offset``; with ``coefficients`` one int16 tensor instead, file i's coefficients behind those of the files
+    before it (the call stopped behind the entropy decode and the DC sums).  ``status``: int32 [N] device tensor, 0 = decoded
+    (JPEG_CORRUPT, JPEG_NOT_CONVERGED otherwise: the pixels then mean nothing).  Nothing is synchronised.  ``subseq_bytes``:
+    the bytes per subsequence of the entropy decode, 0 = the default."""
+    _need_cuda(blob, descs_dev)
+    n = len(descs)
+    if blob.dtype != torch.uint8 or descs_dev.dtype != torch.uint8 or not blob.is_contiguous() or not descs_dev.is_contiguous():
+        raise RuntimeError("jpeg_decode: contiguous uint8 tensors expected")
+    if n < 1 or descs_dev.numel() != n * C.sizeof(_lib.JpegDesc):
+        raise RuntimeError("jpeg_decode: %d descriptors on the host, %d bytes of them on the device" % (n, descs_dev.numel()))
+    lib = _lib.load()
+    nbytes = _size(lib.cgan_jpeg_decode_workspace_bytes(C.addressof(descs), n, int(subseq_bytes)),
+                   "cgan_jpeg_decode_workspace_bytes")
+    ws = _empty(nbytes, dtype=torch.uint8, device=blob.device)
+    status = _empty((n,), dtype=torch.int32, device=blob.device)
+    if coefficients:
+        out = _empty((64 * sum(jpeg_blocks(d) for d in descs),), dtype=torch.int16, device=blob.device)
+        _lib.check(lib.cgan_jpeg_decode_coefficients(_ptr(blob), blob.numel(), C.addressof(descs), _ptr(descs_dev), n,
+                                                     int(subseq_bytes), _ptr(out), out.numel(), _ptr(status), _ptr(ws), nbytes,
+                                                     _stream()), "cgan_jpeg_decode_coefficients")
+    else:
+        out = _empty((max(d.out_offset + d.width * d.height * d.ncomp for d in descs),), dtype=torch.uint8, device=blob.device)
+        _lib.check(lib.cgan_jpeg_decode_u8(_ptr(blob), blob.numel(), C.addressof(descs), _ptr(descs_dev), n, int(subseq_bytes),
+                                           _ptr(out), out.numel(), _ptr(status), _ptr(ws), nbytes, _stream()),
+                   "cgan_jpeg_decode_u8")
+    return out, status
+
+
 def smog(x: torch.Tensor, depth: NHWC, airlight: float, beta: float, alpha: float, yellow_rgb01) -> torch.Tensor:
     """Smog event (reference trainer.py:1879-1939): x NCHW fp32 in [-1, 1], depth the decoder's 1-channel NHWC map;
     returns the smogged image, NCHW fp32."""

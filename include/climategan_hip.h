@@ -692,6 +692,60 @@ int cgan_jpeg_tables(int32_t quality, uint8_t* luma, uint8_t* chroma);
 int cgan_jpeg_scan_host(const int16_t* coef, int32_t h, int32_t w, int32_t c, int32_t quality, int32_t subsampling,
                         uint8_t* out, size_t cap, size_t* size);
 
+/* JPEG decoder on the device: baseline sequential Huffman files (SOF0, 8 bits, one interleaved scan, grey or
+ * YCbCr 4:4:4 / 4:2:2 / 4:2:0, any DHT / DRI, width and height 1 .. 8192) -> uint8 [h][w][c] pixels.
+ *   The status of a file is a set of bits: 0 = decoded.  UNSUPPORTED is decided by the parser alone, on the host, and nothing
+ *   is launched for such a file.  CORRUPT: an invalid code, a restart interval whose block count is not the one the header
+ *   implies, padding that is not 0 .. 7 one-bits.  NOT_CONVERGED: the subsequence states did not reach their fixpoint within
+ *   the launch cap; the other bits of such a word mean nothing.  A file with a non-zero status must be decoded elsewhere. */
+#define CGAN_JPEG_OK 0
+#define CGAN_JPEG_UNSUPPORTED 1
+#define CGAN_JPEG_CORRUPT 2
+#define CGAN_JPEG_NOT_CONVERGED 4
+#define CGAN_JPEG_MAX_DIM 8192
+/* A Huffman table in the decode form: a code of l bits is the next symbol iff the next 16 bits of the stream, as a number, are
+ * below limit[l] and not below limit[l - 1]; the symbol is vals[((those 16 bits >> (16 - l)) + offset[l]) & 255]. */
+typedef struct cgan_jpeg_hufftab {
+  uint32_t limit[17];
+  int32_t offset[17];
+  uint8_t vals[256];
+} cgan_jpeg_hufftab;
+/* One file, as cgan_jpeg_parse_host fills it.  hs, vs: the luma sampling factors (1x1, 2x1, 2x2; chroma is 1x1);
+ * restart_interval in MCUs, 0 = none; the entropy-coded data is scan_bytes bytes from scan_offset of the file (up to, not
+ * including, EOI); quant: per component, natural order.  blob_offset / out_offset are the caller's: where the file's first
+ * byte stands in the input blob and where its first pixel goes in the output blob of the device calls. */
+typedef struct cgan_jpeg_desc {
+  int32_t width, height, ncomp, hs, vs, restart_interval;
+  uint32_t scan_offset, scan_bytes;
+  int64_t blob_offset, out_offset;
+  uint8_t quant[3][64];
+  cgan_jpeg_hufftab dc[3], ac[3];
+} cgan_jpeg_desc;
+/* Host only.  cgan_jpeg_parse_host: the bytes of one file -> *desc and *status (OK, UNSUPPORTED or CORRUPT; the reason in
+ * cgan_last_error).  Returns CGAN_OK whenever it could look at the file; blob_offset / out_offset are set to 0.
+ * cgan_jpeg_decode_coefficients_host: the entropy decode of the device (csrc/jpeg_decode_core.h: the functions the kernels
+ * run), its rounds taken serially: subsequences of subseq_bytes bytes (0: the default, 128; 4 .. 4096), at most round_cap
+ * rounds (0: no cap) -> coef: int16 [blocks * 64] in the layout of cgan_jpeg_coefficients_u8 with luma hs x vs blocks per MCU
+ * (coef_count: the values coef holds, at least that many), *status, *rounds: the rounds after which no state changed. */
+int cgan_jpeg_parse_host(const uint8_t* file, size_t file_bytes, cgan_jpeg_desc* desc, int32_t* status);
+int cgan_jpeg_decode_coefficients_host(const uint8_t* file, size_t file_bytes, const cgan_jpeg_desc* desc,
+                                       int32_t subseq_bytes, int32_t round_cap, int16_t* coef, size_t coef_count,
+                                       int32_t* rounds, int32_t* status);
+/* Device.  blob: the files' bytes, file i from descs[i].blob_offset; descs_host / descs_dev: the same n descriptors in host
+ * and in device memory; out: file i's pixels [h][w][c] from out + descs[i].out_offset; status: n device words (written by the
+ * call); workspace: 16-byte aligned, cgan_jpeg_decode_workspace_bytes(descs_host, n, subseq_bytes).  Everything goes to
+ * `stream` and nothing is synchronised; a call takes at most 15 launches and memsets.  Descriptors that the
+ * parser would not have produced, or ranges outside blob / out: CGAN_ERR_BAD_ARG, nothing launched.
+ * cgan_jpeg_decode_coefficients: the same call stopped behind the entropy decode and the DC sums; coef receives file i's
+ * coefficients from 64 * (the blocks of the files before it). */
+size_t cgan_jpeg_decode_workspace_bytes(const cgan_jpeg_desc* descs_host, int32_t n, int32_t subseq_bytes);
+int cgan_jpeg_decode_u8(const uint8_t* blob, size_t blob_bytes, const cgan_jpeg_desc* descs_host,
+                        const cgan_jpeg_desc* descs_dev, int32_t n, int32_t subseq_bytes, uint8_t* out, size_t out_bytes,
+                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int cgan_jpeg_decode_coefficients(const uint8_t* blob, size_t blob_bytes, const cgan_jpeg_desc* descs_host,
+                                  const cgan_jpeg_desc* descs_dev, int32_t n, int32_t subseq_bytes, int16_t* coef,
+                                  size_t coef_count, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Smog event (Trainer.compute_smog, climategan/trainer.py:1879-1939, parameters shared/trainer/events.yaml:9-14):
  * irradiance = srgb2lrgb(normalize(x)) (tutils.py:534-538), depth = normalize(1 / normalize(d, 0.3, 1), 0.1, 1)
  * bilinearly resized (align_corners=True) to (h, w), transmission = exp(-beta depth),
