@@ -16,7 +16,8 @@ written batch by batch rather than all held in memory; ``--dtype`` selects the k
 the device PNG encoder for smaller files (same pixels; neither is an option of the reference's script); ``--format jpg``
 writes the events and the input picture as baseline JPEG files from the device encoder (``jpeg.write``, DESIGN 4.19;
 ``--jpeg_quality``, ``--jpeg_subsampling``) -- several times smaller, lossy; the masks stay PNG; ``--decode device`` uploads
-baseline JPEG inputs as file bytes and decodes them with the device decoder (``jpeg.decode``).
+baseline JPEG and 8-bit RGB PNG inputs as file bytes and decodes them with the device decoders (``jpeg.decode``, DESIGN 4.20;
+``png.decode``).
 """
 import argparse
 import shutil
@@ -155,8 +156,9 @@ def parse_args(argv=None):
                         help="With --format jpg: chroma at full resolution (444) or halved both ways (420). Defaults to 444")
     parser.add_argument("--decode", default=argparse.SUPPRESS, choices=("host", "device"),
                         help="Not an option of the reference's script: where the input files are decoded. device: baseline "
-                        "JPEG files are uploaded as bytes and decoded by the device decoder; every other file, and any the "
-                        "device reports as corrupt, is read on the host as with host. Defaults to host")
+                        "JPEG files and 8-bit RGB PNG files are uploaded as bytes and decoded by the device decoders; every "
+                        "other file (RGBA, interlaced or palette PNG, progressive JPEG), and any the device reports as "
+                        "corrupt, is read on the host as with host. Defaults to host")
     args = parser.parse_args(argv, namespace=_Args())
     given = vars(args)
     if args.format != "jpg" and ("jpeg_quality" in given or "jpeg_subsampling" in given):
@@ -285,19 +287,21 @@ def read_image(path):
 
 def read_images(paths, decode="host", device="cuda"):
     """The batch's images, each uint8 [H, W, 3]: host arrays from ``read_image``, or with ``decode="device"`` device tensors
-    from ``jpeg.decode`` for the files ``jpeg.probe`` accepts as 3-component baseline JPEG.  Everything else --
-    PNG, progressive JPEG, a file the device reports as corrupt or not converged -- goes through ``read_image`` unchanged;
-    a grey JPEG is refused with ``read_image``'s message in both modes."""
+    from ``jpeg.decode`` for the files ``jpeg.probe`` accepts as 3-component baseline JPEG and from
+    ``png.decode`` for those ``png.probe`` accepts as 8-bit RGB.  Everything else -- RGBA (blended on the host),
+    interlaced or palette PNG, progressive JPEG, a file the device reports as corrupt or not converged -- goes through
+    ``read_image`` unchanged; a grey file is refused with ``read_image``'s message in both modes."""
     if decode != "device":
         return [read_image(p) for p in paths]
-    from . import jpeg
+    from . import jpeg, png
 
     datas = [Path(p).read_bytes() for p in paths]
     images = [None] * len(paths)
-    pick = [i for i, data in enumerate(datas) if getattr(jpeg.probe(data)[0], "ncomp", 0) == 3]
-    if pick:
-        for i, im in zip(pick, jpeg.try_decode([datas[i] for i in pick], device=device)[0]):
-            images[i] = im
+    for codec, channels in ((jpeg, "ncomp"), (png, "channels")):
+        pick = [i for i, data in enumerate(datas) if getattr(codec.probe(data)[0], channels, 0) == 3]
+        if pick:
+            for i, im in zip(pick, codec.try_decode([datas[i] for i in pick], device=device)[0]):
+                images[i] = im
     return [read_image(p) if im is None else im for p, im in zip(paths, images)]
 
 

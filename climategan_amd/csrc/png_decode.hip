@@ -1,0 +1,284 @@
+// PNG decoder on the device: a batch of files' zlib streams in one device blob -> one [h, w, c] image per file
+// and one status word per file.  The parser (host), the bit reader, the code tables, the inflate step, the unfilter arithmetic
+// and the Adler sums are png_decode_core.h: the kernels below call them, the host twin (cgan_png_decode_host) runs the same
+// functions serially.
+//
+//   layout_kernel    one thread: every file's place in the workspace (a prefix sum over the files)
+//   inflate_kernel   one workgroup of one wave per file: the batch is the parallelism.  Lane 0 decodes up to 64 tokens into
+//                    LDS (decode_tokens; the code tables are in LDS, the bit window in its registers); then the wave executes
+//                    them in the stream's order: a prefix sum over the tokens' lengths gives every token its place, each run
+//                    of literals is scattered at once, each match or stored run is copied by the 64 lanes (a match whose
+//                    distance is shorter than its length as a modular repeat).  The last 32 KiB of output are kept in an LDS
+//                    ring, which is all a match ever reads; the workspace is only written.  Nothing is written to the ring
+//                    ahead of its turn: a byte written early would take the slot of the byte 32 KiB before it, which a match
+//                    still to come may read.  Leaves the stream's Adler-32 trailer.
+//   unfilter_kernel  one wave per file, 64 rows at a time as a skewed wavefront: lane r is at pixel t - r in step t, its left
+//                    neighbour is its own last result, the two pixels above come from lane r - 1 by __shfl_up; lane 0 reads
+//                    the previous group's last row from LDS, where lane 63 left it.  Sums the Adler-32 of the bytes it reads
+//                    anyway, row by row, and compares it with the trailer.  Writes the tight pixels.
+// Launches and memsets per call: 1 memset (status) + layout + inflate + unfilter = 4.
+//
+// Bounds: the reader never touches a byte outside [stream, stream + stream_bytes) (Reader::word); decode_tokens hands out a
+// token only if its bytes end inside the file's inflated extent and its source starts at or behind the output's start; a
+// stored run's source is checked against the stream's end.  Loops: a round of inflate_kernel either brings 64 tokens, each of
+// which consumed a bit, or is the last; the copies are bounded by a token's length, the wavefront by the image's size.  No wave
+// waits for another: the only barriers are __syncthreads() of a one-wave workgroup, reached by all lanes (every branch around
+// them depends on values all lanes share).
+#include "cgan_common.h"
+#include "png_decode_host.h"
+
+namespace {
+
+using namespace png_dec;
+
+constexpr int T = 64;                         // one wave
+constexpr uint32_t BATCH = 64;                // tokens per round: one per lane
+constexpr int PREFETCH = 8;                   // steps of the wavefront whose bytes are loaded together
+
+struct Workspace {
+  uint64_t* layout;                           // per file: where its inflated bytes start in `inflated`
+  uint32_t* adler;                            // per file: the trailer the stream had
+  uint8_t* inflated;
+  size_t bytes;
+};
+inline size_t align16(size_t v) { return (v + 15) / 16 * 16; }
+// the same arithmetic for the size query and the call
+Workspace carve(void* base, const cgan_png_desc* descs, int32_t n) {
+  Workspace w;
+  char* p = static_cast<char*>(base);
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    char* q = p + at;
+    at += align16(bytes);
+    return q;
+  };
+  w.layout = reinterpret_cast<uint64_t*>(take(sizeof(uint64_t) * (size_t)n));
+  w.adler = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * (size_t)n));
+  size_t total = 0;
+  for (int32_t i = 0; i < n; ++i) total += align16(inflated_bytes(descs[i]));
+  w.inflated = reinterpret_cast<uint8_t*>(take(total));
+  w.bytes = at;
+  return w;
+}
+
+__global__ void layout_kernel(const cgan_png_desc* __restrict__ descs, int n, uint64_t* __restrict__ layout) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  uint64_t at = 0;
+  for (int i = 0; i < n; ++i) {
+    layout[i] = at;
+    at += ((uint64_t)inflated_bytes(descs[i]) + 15) / 16 * 16;
+  }
+}
+
+__global__ __launch_bounds__(T) void inflate_kernel(const uint8_t* __restrict__ blob, const cgan_png_desc* __restrict__ descs,
+                                                    Workspace w, int32_t* __restrict__ status) {
+  __shared__ Tables tables;
+  __shared__ Token tok[BATCH];
+  __shared__ uint32_t ctl[2];                 // tokens of the round; whether another round follows
+  __shared__ uint8_t ring[WINDOW];
+  const int file = blockIdx.x;
+  const uint32_t lane = threadIdx.x;
+  const cgan_png_desc d = descs[file];
+  const uint8_t* stream = blob + d.blob_offset;
+  uint8_t* out = w.inflated + w.layout[file];
+  Inflate s;
+  s.start(stream, d.stream_bytes, inflated_bytes(d));   // every lane the same; lane 0's is the one that advances
+  uint32_t pos = 0;                                     // bytes executed so far, the same in every lane
+  for (;;) {
+    if (lane == 0) {
+      ctl[0] = decode_tokens(s, tables, tok, BATCH);
+      ctl[1] = (s.phase != PHASE_DONE && !s.err) ? 1u : 0u;
+    }
+    __syncthreads();
+    const uint32_t nt = ctl[0] < BATCH ? ctl[0] : BATCH;
+    const bool more = ctl[1] != 0 && nt == BATCH;       // a round that is not full is the last one
+    Token k{0, 0, 0, 0};
+    if (lane < nt) k = tok[lane];
+    uint32_t incl = k.len;
+    for (int off = 1; off < T; off <<= 1) {
+      const uint32_t v = __shfl_up(incl, off);
+      if ((int)lane >= off) incl += v;
+    }
+    const uint32_t mine = pos + incl - k.len;           // where my token's bytes go: inside the extent (decode_tokens)
+    // in the stream's order: the literals up to the next match or stored run at once, then that token by all lanes
+    unsigned long long todo = __ballot(lane < nt && k.kind != TOK_LITERAL);
+    int done = -1;                                      // the tokens up to this one are executed
+    while (todo) {                                      // at most 64 turns, the same in every lane
+      const int i = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      if ((int)lane > done && (int)lane < i) {          // literals all: the tokens between two set bits
+        ring[mine & (WINDOW - 1)] = k.lit;
+        out[mine] = k.lit;
+      }
+      __syncthreads();
+      const Token m = tok[i & (BATCH - 1)];
+      const uint32_t q = __shfl(mine, i);
+      if (m.kind == TOK_MATCH) {
+        const uint32_t from = q - m.arg;                // m.arg <= q: decode_tokens checked it
+        for (uint32_t j = lane; j < m.len; j += T) {
+          const uint8_t v = ring[(from + (m.arg < m.len ? j % m.arg : j)) & (WINDOW - 1)];
+          ring[(q + j) & (WINDOW - 1)] = v;
+          out[q + j] = v;
+        }
+      } else {
+        for (uint32_t j = lane; j < m.len; j += T) {    // m.arg + m.len <= stream_bytes: block_header checked it
+          const uint8_t v = stream[m.arg + j];
+          ring[(q + j) & (WINDOW - 1)] = v;
+          out[q + j] = v;
+        }
+      }
+      __syncthreads();
+      done = i;
+    }
+    if ((int)lane > done && lane < nt) {                // the literals behind the last match
+      ring[mine & (WINDOW - 1)] = k.lit;
+      out[mine] = k.lit;
+    }
+    pos += __shfl(incl, T - 1);
+    __syncthreads();
+    if (!more) break;
+  }
+  if (lane == 0) {
+    if (s.err || s.phase != PHASE_DONE) atomicOr(&status[file], (int32_t)CGAN_PNG_CORRUPT);
+    w.adler[file] = s.adler;
+  }
+}
+
+__global__ __launch_bounds__(T) void unfilter_kernel(const cgan_png_desc* __restrict__ descs, Workspace w, uint8_t* __restrict__ out_base,
+                                                     int32_t* __restrict__ status) {
+  __shared__ uint32_t above[CGAN_PNG_MAX_DIM];          // the last row of the group before, a pixel per word
+  const int file = blockIdx.x;
+  const int lane = threadIdx.x;
+  if (status[file] != 0) return;                        // the whole wave: the inflate failed, there is nothing to unfilter
+  const cgan_png_desc d = descs[file];
+  const int W = d.width, H = d.height;
+  const uint32_t bpp = bytes_per_pixel(d), rb = row_bytes(d), total = inflated_bytes(d);
+  const bool swap = d.bit_depth == 16;
+  const uint8_t* in = w.inflated + w.layout[file];
+  uint8_t* out = out_base + d.out_offset;
+  Adler ad;
+  ad.start();
+  bool bad = false;
+  for (int g = 0; g * T < H; ++g) {
+    const int y = g * T + lane;
+    const bool live = y < H;
+    const uint8_t* row = in + (size_t)(live ? y : 0) * (1 + rb);
+    const uint32_t filter = live ? row[0] : 0u;
+    if (live) ad.byte(filter);
+    bad = bad || filter > 4;
+    uint32_t cur = 0, prev = 0, above_left = 0;         // my results of the last step and the one before; lane 0: its last b
+    for (int t0 = 0; t0 < W + T - 1; t0 += PREFETCH) {
+      uint32_t raw[PREFETCH];
+#pragma unroll
+      for (int u = 0; u < PREFETCH; ++u) {
+        const int x = t0 + u - lane;
+        raw[u] = 0;
+        if (live && x >= 0 && x < W)
+          for (uint32_t k = 0; k < bpp; ++k) raw[u] |= (uint32_t)row[1 + (uint32_t)x * bpp + k] << (8 * k);
+      }
+#pragma unroll
+      for (int u = 0; u < PREFETCH; ++u) {
+        const int x = t0 + u - lane;
+        const bool active = live && x >= 0 && x < W;
+        uint32_t b = __shfl_up(cur, 1), c = __shfl_up(prev, 1);
+        if (lane == 0) {
+          c = above_left;
+          b = (g > 0 && x < W) ? above[x & (CGAN_PNG_MAX_DIM - 1)] : 0u;
+          above_left = b;
+        }
+        const uint32_t v = active ? unfilter_pixel(filter, raw[u], cur, b, c) : 0u;
+        if (active) {
+          uint8_t* px = out + ((size_t)y * W + x) * bpp;
+          for (uint32_t k = 0; k < bpp; ++k) {
+            px[swap ? 1 - k : k] = (uint8_t)(v >> (8 * k));
+            ad.byte((raw[u] >> (8 * k)) & 255u);
+          }
+          if (lane == T - 1) above[x & (CGAN_PNG_MAX_DIM - 1)] = v;
+        }
+        prev = cur, cur = v;
+      }
+    }
+    if (live) ad.end_piece(total - (uint32_t)(y + 1) * (1 + rb));
+    __syncthreads();
+  }
+  uint32_t s1 = ad.s1, s2 = ad.s2;
+  for (int off = 1; off < T; off <<= 1) {
+    s1 = (s1 + __shfl_xor(s1, off)) % ADLER_MOD;
+    s2 = (s2 + __shfl_xor(s2, off)) % ADLER_MOD;
+  }
+  const bool any_bad = __ballot(bad) != 0;
+  if (lane == 0 && (any_bad || adler_value(s1, s2, total) != w.adler[file])) atomicOr(&status[file], (int32_t)CGAN_PNG_CORRUPT);
+}
+
+int descs_ok(const char* what, const cgan_png_desc* descs, int32_t n, size_t blob_bytes, bool with_out, size_t out_bytes) {
+  CGAN_REQUIRE(descs, "%s: null pointer", what);
+  CGAN_REQUIRE(n >= 1 && n <= 65535, "%s: n = %d: 1 <= n <= 65535 expected", what, n);
+  for (int32_t i = 0; i < n; ++i) {
+    const cgan_png_desc& d = descs[i];
+    CGAN_REQUIRE(desc_ok(d), "%s: descriptor %d is not one the parser produces", what, i);
+    CGAN_REQUIRE(d.blob_offset >= 0 && d.blob_offset % 4 == 0 && (uint64_t)d.blob_offset + d.stream_bytes <= blob_bytes,
+                 "%s: the stream of file %d is not 4-byte aligned or reaches behind the blob's end", what, i);
+    if (with_out)
+      CGAN_REQUIRE(d.out_offset >= 0 && d.out_offset % (d.bit_depth / 8) == 0 &&
+                       (uint64_t)d.out_offset + pixel_bytes(d) <= out_bytes,
+                   "%s: the pixels of file %d are misaligned or reach behind the output's end", what, i);
+  }
+  return CGAN_OK;
+}
+
+}  // namespace
+
+extern "C" int cgan_png_parse_host(const uint8_t* file, size_t file_bytes, cgan_png_desc* desc, int32_t* status) {
+  char why[160] = "";
+  const int rc = host_parse(file, file_bytes, desc, status, why, sizeof(why));
+  if (rc || *status) cgan_set_error("cgan_png_parse_host: %s", why);
+  return rc ? CGAN_ERR_BAD_ARG : CGAN_OK;
+}
+
+extern "C" int cgan_png_stream_host(const uint8_t* file, size_t file_bytes, const cgan_png_desc* desc, uint8_t* dst,
+                                    size_t dst_bytes) {
+  char why[160] = "";
+  const int rc = host_stream(file, file_bytes, desc, dst, dst_bytes, why, sizeof(why));
+  if (rc) cgan_set_error("cgan_png_stream_host: %s", why);
+  return rc ? CGAN_ERR_BAD_ARG : CGAN_OK;
+}
+
+extern "C" int cgan_png_decode_host(const uint8_t* stream, const cgan_png_desc* desc, uint8_t* inflated, uint8_t* pixels,
+                                    int32_t* status) {
+  char why[160] = "";
+  const int rc = host_decode(stream, desc, inflated, pixels, status, why, sizeof(why));
+  if (rc || *status) cgan_set_error("cgan_png_decode_host: %s", why);
+  return rc ? CGAN_ERR_BAD_ARG : CGAN_OK;
+}
+
+extern "C" size_t cgan_png_decode_workspace_bytes(const cgan_png_desc* descs_host, int32_t n) {
+  if (descs_ok("cgan_png_decode_workspace_bytes", descs_host, n, ~(size_t)0, false, 0)) return 0;
+  return carve(nullptr, descs_host, n).bytes;
+}
+
+extern "C" int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
+                               const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  const char* what = "cgan_png_decode";
+  CGAN_REQUIRE(blob && descs_dev && out && status && workspace, "%s: null pointer", what);
+  if (const int rc = descs_ok(what, descs_host, n, blob_bytes, true, out_bytes)) return rc;
+  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(blob) % 4 == 0, "%s: the blob is not 4-byte aligned", what);
+  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: the workspace is not 16-byte aligned", what);
+  const Workspace w = carve(workspace, descs_host, n);
+  if (w.bytes > workspace_bytes) {
+    cgan_set_error("%s: the workspace has %zu bytes, %zu are needed", what, workspace_bytes, w.bytes);
+    return CGAN_ERR_WORKSPACE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)n, s) != hipSuccess) {
+    cgan_set_error("%s: hipMemsetAsync failed", what);
+    return CGAN_ERR_HIP;
+  }
+  hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(64), 0, s, descs_dev, n, w.layout);
+  CGAN_CHECK_LAUNCH("cgan_png_decode (layout)");
+  hipLaunchKernelGGL(inflate_kernel, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status);
+  CGAN_CHECK_LAUNCH("cgan_png_decode (inflate)");
+  hipLaunchKernelGGL(unfilter_kernel, dim3(n), dim3(T), 0, s, descs_dev, w, out, status);
+  CGAN_CHECK_LAUNCH("cgan_png_decode (unfilter)");
+  return CGAN_OK;
+}

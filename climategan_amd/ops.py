@@ -787,6 +787,34 @@ def jpeg_decode(blob: torch.Tensor, descs, descs_dev: torch.Tensor, subseq_bytes
     return out, status
 
 
+PNG_DECODE_MAX_DIM = 8192    # the widest and the highest file cgan_png_decode takes
+PNG_OK, PNG_UNSUPPORTED, PNG_CORRUPT = 0, 1, 2      # a file's status bits (climategan_hip.h)
+
+
+def png_decode(blob: torch.Tensor, descs, descs_dev: torch.Tensor):
+    """The device PNG decoder.  ``blob``: uint8 device tensor with the files' zlib streams (the IDAT payloads
+    as ``cgan_png_stream_host`` joins them); ``descs``: a ctypes array of ``_lib.PngDesc`` as ``cgan_png_parse_host`` filled
+    them, ``blob_offset`` (a multiple of 4) / ``out_offset`` set by the caller; ``descs_dev``: the same bytes as a uint8 device
+    tensor -> (out, status).  ``out``: one uint8 tensor, file i's [H, W, C] pixels from ``out_offset`` (16-bit grey: two bytes
+    a pixel in host order).  ``status``: int32 [N] device tensor, 0 = decoded (PNG_CORRUPT otherwise: the pixels then mean
+    nothing).  Nothing is synchronised."""
+    _need_cuda(blob, descs_dev)
+    n = len(descs)
+    if blob.dtype != torch.uint8 or descs_dev.dtype != torch.uint8 or not blob.is_contiguous() or not descs_dev.is_contiguous():
+        raise RuntimeError("png_decode: contiguous uint8 tensors expected")
+    if n < 1 or descs_dev.numel() != n * C.sizeof(_lib.PngDesc):
+        raise RuntimeError("png_decode: %d descriptors on the host, %d bytes of them on the device" % (n, descs_dev.numel()))
+    lib = _lib.load()
+    nbytes = _size(lib.cgan_png_decode_workspace_bytes(C.addressof(descs), n), "cgan_png_decode_workspace_bytes")
+    ws = _empty(nbytes, dtype=torch.uint8, device=blob.device)
+    status = _empty((n,), dtype=torch.int32, device=blob.device)
+    out = _empty((max(d.out_offset + d.width * d.height * d.channels * (d.bit_depth // 8) for d in descs),), dtype=torch.uint8,
+                 device=blob.device)
+    _lib.check(lib.cgan_png_decode(_ptr(blob), blob.numel(), C.addressof(descs), _ptr(descs_dev), n, _ptr(out), out.numel(),
+                                   _ptr(status), _ptr(ws), nbytes, _stream()), "cgan_png_decode")
+    return out, status
+
+
 def smog(x: torch.Tensor, depth: NHWC, airlight: float, beta: float, alpha: float, yellow_rgb01) -> torch.Tensor:
     """Smog event (reference trainer.py:1879-1939): x NCHW fp32 in [-1, 1], depth the decoder's 1-channel NHWC map;
     returns the smogged image, NCHW fp32."""

@@ -1,8 +1,18 @@
 """PNG files from uint8 device images: ``ops.png_encode`` (csrc/png.hip) builds the files on the device,
 ``_files`` brings their bytes to the host (two waits, only the compressed bytes cross PCIe) and writes them.  There is no
 host encoder behind it: a CPU tensor is refused.
+
+The other way: ``probe`` reads a file's chunks on the host, ``decode`` uploads a batch of files' zlib streams
+and inflates and unfilters them on the device (``ops.png_decode``), one wave per file.
 """
-from . import _files, ops
+import ctypes as C
+from pathlib import Path
+
+import torch
+
+from . import _files, _lib, ops
+
+STATUS_TEXT = {ops.PNG_UNSUPPORTED: "unsupported", ops.PNG_CORRUPT: "corrupt data"}
 
 
 def encode(img_u8, level=1):
@@ -14,3 +24,95 @@ def encode(img_u8, level=1):
 def write(img_u8, paths, level=1):
     """Encode a batch on the device (at ``level``, see ``ops.png_encode``) and write image i to ``paths[i]``."""
     _files.write_files("png.write", *_files.fetch(*ops.png_encode(img_u8, level)), paths)
+
+
+def probe(data):
+    """The bytes of one file -> (descriptor, None) if the device decoder takes it (a ``_lib.PngDesc``: width, height,
+    channels, bit depth, the length of its zlib stream), else (None, reason): not a PNG file, a kind of PNG outside DESIGN
+    4.21's list (interlaced, palette, grey + alpha, fewer than 8 bits, 16-bit colour, animated), or broken chunks.  Host
+    only."""
+    data = bytes(data)
+    lib = _lib.load()
+    d, status = _lib.PngDesc(), C.c_int32(0)
+    _lib.check(lib.cgan_png_parse_host(data, len(data), C.addressof(d), C.addressof(status)), "cgan_png_parse_host")
+    if status.value != ops.PNG_OK:
+        return None, lib.cgan_last_error().decode()
+    return d, None
+
+
+def stream_of(data, d):
+    """The zlib stream of a probed file: its IDAT payloads one behind the other, as ``bytes``.  Host only."""
+    data = bytes(data)
+    buf = C.create_string_buffer(max(d.stream_bytes, 1))
+    _lib.check(_lib.load().cgan_png_stream_host(data, len(data), C.addressof(d), buf, d.stream_bytes), "cgan_png_stream_host")
+    return buf.raw[:d.stream_bytes]
+
+
+def _pixel_bytes(d):
+    return d.width * d.height * d.channels * (d.bit_depth // 8)
+
+
+def upload(descs_and_data, device):
+    """[(descriptor, the file's bytes)] -> (blob, descs, descs_dev) as ``ops.png_decode`` takes them: the files' zlib streams
+    16-byte aligned in one blob, the pixels 16-byte aligned in one output, one upload each for the bytes and for the
+    descriptors."""
+    descs = (_lib.PngDesc * len(descs_and_data))()
+    blob, out_at = bytearray(), 0
+    for k, (d, data) in enumerate(descs_and_data):
+        d.blob_offset, d.out_offset = len(blob), out_at
+        blob += stream_of(data, d)
+        blob += bytes(-len(blob) % 16)
+        out_at += -(-_pixel_bytes(d) // 16) * 16
+        descs[k] = d
+    return (torch.frombuffer(blob, dtype=torch.uint8).to(device), descs,
+            torch.frombuffer(bytearray(descs), dtype=torch.uint8).to(device))
+
+
+def try_decode(files, device="cuda"):
+    """``decode`` without raising for a file's sake -> (images, reasons): ``images[i]`` is None for a file that was not
+    decoded and ``reasons[i]`` says why."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("png.decode needs a device (got %s); there is no CPU path" % device)
+    datas = [bytes(f) if isinstance(f, (bytes, bytearray, memoryview)) else Path(f).read_bytes() for f in files]
+    images, reasons, taken = [None] * len(datas), {}, []
+    for i, data in enumerate(datas):
+        d, why = probe(data)
+        if d is None:
+            reasons[i] = why
+        else:
+            taken.append((i, d))
+    if taken:
+        blob, descs, descs_dev = upload([(d, datas[i]) for i, d in taken], device)
+        out, status = ops.png_decode(blob, descs, descs_dev)
+        for (i, _), d, s in zip(taken, descs, status.tolist()):               # the one wait
+            if s != ops.PNG_OK:
+                reasons[i] = STATUS_TEXT[ops.PNG_CORRUPT]
+            else:
+                px = out[d.out_offset:d.out_offset + _pixel_bytes(d)]
+                if d.bit_depth == 16:
+                    px = px.view(torch.uint16)
+                images[i] = px.view(d.height, d.width, d.channels)
+    return images, reasons
+
+
+def decode(files, fallback=False, device="cuda"):
+    """``files``: a list of ``bytes`` or paths of PNG files -> a list of device tensors, views into one allocation: uint8
+    [H, W, C] with C = 1, 3 or 4, and ``torch.uint16`` [H, W, 1] for 16-bit grey.  One upload of the bytes, one of the
+    descriptors, one wait (for the status words).  A file the decoder does not take (``probe``) or reports as corrupt raises
+    ``RuntimeError`` with its index and the reason -- unless ``fallback``: that file is then decoded by PIL on the host and
+    uploaded."""
+    images, reasons = try_decode(files, device)
+    if reasons and not fallback:
+        i = min(reasons)
+        raise RuntimeError("png.decode: file %d: %s" % (i, reasons[i]))
+    for i in reasons:
+        import io
+
+        import numpy as np
+        from PIL import Image
+
+        f = files[i]
+        a = np.asarray(Image.open(io.BytesIO(bytes(f)) if isinstance(f, (bytes, bytearray, memoryview)) else f))
+        images[i] = torch.from_numpy(a.reshape(a.shape[0], a.shape[1], -1).copy()).to(device)
+    return images

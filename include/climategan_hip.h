@@ -746,6 +746,44 @@ int cgan_jpeg_decode_coefficients(const uint8_t* blob, size_t blob_bytes, const 
                                   const cgan_jpeg_desc* descs_dev, int32_t n, int32_t subseq_bytes, int16_t* coef,
                                   size_t coef_count, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* PNG decoder on the device: non-interlaced files of bit depth 8 with colour type 0, 2 or 6 (grey, RGB, RGBA)
+ * and of bit depth 16 with colour type 0, width and height 1 .. 8192, any IDAT chunking, stored / fixed / dynamic deflate
+ * blocks -> the pixels PIL returns: uint8 [h][w][c], or uint16 [h][w][1] in host byte order for 16-bit grey.
+ *   The status of a file is a set of bits: 0 = decoded.  UNSUPPORTED is decided by the parser alone, on the host, and nothing
+ *   is launched for such a file.  CORRUPT comes from the parser (chunk structure, the IHDR CRC, the zlib header) or from the
+ *   decode (an invalid deflate stream, an Adler-32 mismatch, a filter byte above 4); the pixels of such a file mean nothing. */
+#define CGAN_PNG_OK 0
+#define CGAN_PNG_UNSUPPORTED 1
+#define CGAN_PNG_CORRUPT 2
+#define CGAN_PNG_MAX_DIM 8192
+/* One file, as cgan_png_parse_host fills it.  channels: 1, 3 or 4; bit_depth: 8, or 16 (channels = 1 only); stream_bytes: the
+ * IDAT payloads together, one zlib stream.  blob_offset / out_offset are the caller's: where the file's zlib stream (as
+ * cgan_png_stream_host copies it; a multiple of 4) stands in the input blob and where its first pixel goes in the output
+ * blob of the device call (a multiple of 2 for 16-bit files). */
+typedef struct cgan_png_desc {
+  int32_t width, height, channels, bit_depth;
+  uint32_t stream_bytes, reserved;
+  int64_t blob_offset, out_offset;
+} cgan_png_desc;
+/* Host only.  cgan_png_parse_host: the bytes of one file -> *desc and *status (OK, UNSUPPORTED or CORRUPT; the reason in
+ * cgan_last_error).  Returns CGAN_OK whenever it could look at the file; blob_offset / out_offset are set to 0.
+ * cgan_png_stream_host: the IDAT payloads of a parsed file one behind the other into dst (dst_bytes >= desc->stream_bytes).
+ * cgan_png_decode_host: the device's decode run serially (csrc/png_decode_core.h: the functions the kernels run) on such a
+ * stream -> inflated: height * (1 + row bytes) bytes, the filter bytes and filtered rows; pixels: height * row bytes bytes as
+ * the device writes them; *status. */
+int cgan_png_parse_host(const uint8_t* file, size_t file_bytes, cgan_png_desc* desc, int32_t* status);
+int cgan_png_stream_host(const uint8_t* file, size_t file_bytes, const cgan_png_desc* desc, uint8_t* dst, size_t dst_bytes);
+int cgan_png_decode_host(const uint8_t* stream, const cgan_png_desc* desc, uint8_t* inflated, uint8_t* pixels, int32_t* status);
+/* Device.  blob: the files' zlib streams, file i's from descs[i].blob_offset; descs_host / descs_dev: the same n descriptors
+ * in host and in device memory; out: file i's pixels from out + descs[i].out_offset; status: n device words (written by the
+ * call); workspace: 16-byte aligned, cgan_png_decode_workspace_bytes(descs_host, n).  Everything goes to `stream` and nothing
+ * is synchronised; a call is one memset and three launches.  Descriptors that the parser would not have
+ * produced, or ranges outside blob / out: CGAN_ERR_BAD_ARG, nothing launched. */
+size_t cgan_png_decode_workspace_bytes(const cgan_png_desc* descs_host, int32_t n);
+int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host, const cgan_png_desc* descs_dev,
+                    int32_t n, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* Smog event (Trainer.compute_smog, climategan/trainer.py:1879-1939, parameters shared/trainer/events.yaml:9-14):
  * irradiance = srgb2lrgb(normalize(x)) (tutils.py:534-538), depth = normalize(1 / normalize(d, 0.3, 1), 0.1, 1)
  * bilinearly resized (align_corners=True) to (h, w), transmission = exp(-beta depth),
