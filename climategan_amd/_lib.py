@@ -68,7 +68,7 @@ class JpegDesc(C.Structure):
 class PngDesc(C.Structure):
     """cgan_png_desc: one PNG file as ``cgan_png_parse_host`` describes it, plus the caller's two offsets."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("bit_depth", C.c_int32),
-                ("stream_bytes", C.c_uint32), ("reserved", C.c_uint32), ("blob_offset", C.c_int64), ("out_offset", C.c_int64)]
+                ("stream_bytes", C.c_uint32), ("rows", C.c_uint32), ("blob_offset", C.c_int64), ("out_offset", C.c_int64)]
 
 
 class AdamItem(C.Structure):
@@ -294,6 +294,11 @@ _SIGNATURES = {
     "cgan_png_decode_host": (C.c_int, [_P, _P, _P, _P, _P]),
     "cgan_png_decode_workspace_bytes": (C.c_size_t, [_P, C.c_int32]),
     "cgan_png_decode": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "cgan_png_row_table_host": (C.c_int, [_P, C.c_size_t, _P, _P]),
+    "cgan_png_decode_rows_host": (C.c_int, [_P] * 7),
+    "cgan_png_decode_rows_workspace_bytes": (C.c_size_t, [_P, _P, C.c_size_t, C.c_int32]),
+    "cgan_png_decode_rows": (C.c_int, [_P, C.c_size_t, _P, _P, _P, _P, C.c_size_t, C.c_int32, _P, C.c_size_t, _P, _P, _P,
+                                       C.c_size_t, _P]),
     "cgan_smog_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "cgan_smog_nchw": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), _P, C.c_size_t, _P]),

@@ -18,6 +18,18 @@
 //                    anyway, row by row, and compares it with the trailer.  Writes the tight pixels.
 // Launches and memsets per call: 1 memset (status) + layout + inflate + unfilter = 4.
 //
+// Row-framed files (cgan_png_decode_rows): files with one IDAT chunk per row, each row coded on its own and ended
+// by a stored block on the chunk's last byte, as this project's encoder writes them (4.17).
+//   layout_rows_kernel   layout_kernel's work, every candidate's place in the table of row offsets, the "refused" words zeroed
+//   inflate_rows_kernel  one workgroup of one wave per (row, file), the tail behind the last row as one more row.  The same
+//                        shape as inflate_kernel -- lane 0 decodes up to 64 tokens (decode_tokens in MODE_ROW: the reader
+//                        bounded to the row's chunk), the wave executes them -- with the row itself as the window, in dynamic
+//                        LDS sized from the batch's longest row.  Whatever a row does not satisfy ORs the file's "refused" word.
+//   inflate_kernel<true> the serial kernel for the files that are no candidates or were refused; the others' workgroups return.
+// Launches and memsets per call: 1 memset (status) + layout + row inflate + serial inflate + unfilter = 5.  The bounds above
+// hold: a row's reader ends with its chunk, a token's bytes end inside the row, a match starts at or behind the row's first
+// byte, the row buffer's indices are reduced modulo its size, the table's offsets are checked on the host and again by the wave.
+//
 // Bounds: the reader never touches a byte outside [stream, stream + stream_bytes) (Reader::word); decode_tokens hands out a
 // token only if its bytes end inside the file's inflated extent and its source starts at or behind the output's start; a
 // stored run's source is checked against the stream's end.  Loops: a round of inflate_kernel either brings 64 tokens, each of
@@ -39,11 +51,13 @@ struct Workspace {
   uint64_t* layout;                           // per file: where its inflated bytes start in `inflated`
   uint32_t* adler;                            // per file: the trailer the stream had
   uint8_t* inflated;
+  uint32_t* table_at;                         // the row calls only, per file: where its offsets start in the table; refused or not
+  uint32_t* refused;
   size_t bytes;
 };
 inline size_t align16(size_t v) { return (v + 15) / 16 * 16; }
 // the same arithmetic for the size query and the call
-Workspace carve(void* base, const cgan_png_desc* descs, int32_t n) {
+Workspace carve(void* base, const cgan_png_desc* descs, int32_t n, bool rows = false) {
   Workspace w;
   char* p = static_cast<char*>(base);
   size_t at = 0;
@@ -57,6 +71,8 @@ Workspace carve(void* base, const cgan_png_desc* descs, int32_t n) {
   size_t total = 0;
   for (int32_t i = 0; i < n; ++i) total += align16(inflated_bytes(descs[i]));
   w.inflated = reinterpret_cast<uint8_t*>(take(total));
+  w.table_at = rows ? reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * (size_t)n)) : nullptr;
+  w.refused = rows ? reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * (size_t)n)) : nullptr;
   w.bytes = at;
   return w;
 }
@@ -70,8 +86,117 @@ __global__ void layout_kernel(const cgan_png_desc* __restrict__ descs, int n, ui
   }
 }
 
+__global__ void layout_rows_kernel(const cgan_png_desc* __restrict__ descs, int n, Workspace w) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  uint64_t at = 0;
+  uint32_t words = 0;
+  for (int i = 0; i < n; ++i) {
+    w.layout[i] = at;
+    at += ((uint64_t)inflated_bytes(descs[i]) + 15) / 16 * 16;
+    w.table_at[i] = words;
+    words += table_words(descs[i]);
+    w.refused[i] = 0;
+  }
+}
+
+// One wave per (row, file): blockIdx.x = the row, or the file's height for the tail; blockIdx.y = the file.
+//   table: the candidates' offsets one file behind the other, table_len words in all; cap: the bytes of `row`, at least the
+//   longest 1 + row_bytes of the batch's candidates.
+__global__ __launch_bounds__(T) void inflate_rows_kernel(const uint8_t* __restrict__ blob, const cgan_png_desc* __restrict__ descs,
+                                                         const uint32_t* __restrict__ table, uint32_t table_len, Workspace w,
+                                                         uint32_t cap) {
+  extern __shared__ __align__(16) uint8_t row[];        // the row so far: all a match may read
+  __shared__ Tables tables;
+  __shared__ Token tok[BATCH];
+  __shared__ uint32_t ctl[2];                 // tokens of the round; whether another round follows
+  const int file = blockIdx.y;
+  const uint32_t k = blockIdx.x, lane = threadIdx.x;
+  const cgan_png_desc d = descs[file];
+  if (d.rows == 0 || k > d.rows) return;                // the whole wave: not a candidate, or no such row
+  const uint32_t t0 = w.table_at[file];
+  const bool tail = k == d.rows;
+  const uint32_t limit = tail ? 0u : 1u + row_bytes(d);
+  // the chunk, checked once more where it is used: inside the table, ascending, inside the stream, the row inside the buffer
+  uint32_t begin = 0, end = 0;
+  bool ok = (uint64_t)t0 + d.rows + 1 <= table_len && limit <= cap;
+  if (ok) {
+    begin = table[t0 + k];
+    end = tail ? d.stream_bytes : table[t0 + k + 1];
+    ok = begin <= end && end <= d.stream_bytes;
+  }
+  if (!ok) {                                            // the same in every lane
+    if (lane == 0) atomicOr(&w.refused[file], 1u);
+    return;
+  }
+  const uint8_t* stream = blob + d.blob_offset;
+  uint8_t* out = w.inflated + w.layout[file] + (size_t)(tail ? 0u : k) * limit;
+  Inflate s;
+  s.start_row(stream, begin, end, limit, tail ? MODE_TAIL : MODE_ROW);   // every lane the same; lane 0's is the one that advances
+  uint32_t pos = 0;                                     // bytes executed so far, the same in every lane
+  for (;;) {
+    if (lane == 0) {
+      ctl[0] = decode_tokens(s, tables, tok, BATCH);
+      ctl[1] = (s.phase != PHASE_DONE && !s.err) ? 1u : 0u;
+    }
+    __syncthreads();
+    const uint32_t nt = ctl[0] < BATCH ? ctl[0] : BATCH;
+    const bool more = ctl[1] != 0 && nt == BATCH;       // a round that is not full is the last one
+    Token q{0, 0, 0, 0};
+    if (lane < nt) q = tok[lane];
+    uint32_t incl = q.len;
+    for (int off = 1; off < T; off <<= 1) {
+      const uint32_t v = __shfl_up(incl, off);
+      if ((int)lane >= off) incl += v;
+    }
+    const uint32_t mine = pos + incl - q.len;           // where my token's bytes go: inside the row (decode_tokens)
+    unsigned long long todo = __ballot(lane < nt && q.kind != TOK_LITERAL);
+    int done = -1;
+    while (todo) {                                      // at most 64 turns, the same in every lane
+      const int i = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      if ((int)lane > done && (int)lane < i) {
+        row[mine % cap] = q.lit;
+        out[mine] = q.lit;
+      }
+      __syncthreads();
+      const Token m = tok[i & (BATCH - 1)];
+      const uint32_t at = __shfl(mine, i);
+      if (m.kind == TOK_MATCH) {
+        const uint32_t from = at - m.arg;               // m.arg <= at: decode_tokens checked it against the row's start
+        for (uint32_t j = lane; j < m.len; j += T) {
+          const uint8_t v = row[(from + (m.arg < m.len ? j % m.arg : j)) % cap];
+          row[(at + j) % cap] = v;
+          out[at + j] = v;
+        }
+      } else {
+        for (uint32_t j = lane; j < m.len; j += T) {    // m.arg + m.len <= the chunk's end: block_header checked it
+          const uint8_t v = stream[m.arg + j];
+          row[(at + j) % cap] = v;
+          out[at + j] = v;
+        }
+      }
+      __syncthreads();
+      done = i;
+    }
+    if ((int)lane > done && lane < nt) {
+      row[mine % cap] = q.lit;
+      out[mine] = q.lit;
+    }
+    pos += __shfl(incl, T - 1);
+    __syncthreads();
+    if (!more) break;
+  }
+  if (lane == 0) {
+    if (s.err || s.phase != PHASE_DONE) atomicOr(&w.refused[file], 1u);
+    else if (tail) w.adler[file] = s.adler;
+  }
+}
+
+// PREDICATED (cgan_png_decode_rows): behind inflate_rows_kernel.  A candidate that no row refused is done (path 1); every other
+// file is decoded here (path 0: not a candidate, 2: refused by the row path).
+template <bool PREDICATED>
 __global__ __launch_bounds__(T) void inflate_kernel(const uint8_t* __restrict__ blob, const cgan_png_desc* __restrict__ descs,
-                                                    Workspace w, int32_t* __restrict__ status) {
+                                                    Workspace w, int32_t* __restrict__ status, int32_t* __restrict__ path) {
   __shared__ Tables tables;
   __shared__ Token tok[BATCH];
   __shared__ uint32_t ctl[2];                 // tokens of the round; whether another round follows
@@ -79,6 +204,11 @@ __global__ __launch_bounds__(T) void inflate_kernel(const uint8_t* __restrict__ 
   const int file = blockIdx.x;
   const uint32_t lane = threadIdx.x;
   const cgan_png_desc d = descs[file];
+  if constexpr (PREDICATED) {
+    const bool by_rows = d.rows != 0 && w.refused[file] == 0;       // the same in every lane
+    if (lane == 0) path[file] = by_rows ? 1 : (d.rows != 0 ? 2 : 0);
+    if (by_rows) return;
+  }
   const uint8_t* stream = blob + d.blob_offset;
   uint8_t* out = w.inflated + w.layout[file];
   Inflate s;
@@ -276,9 +406,95 @@ extern "C" int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cga
   }
   hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(64), 0, s, descs_dev, n, w.layout);
   CGAN_CHECK_LAUNCH("cgan_png_decode (layout)");
-  hipLaunchKernelGGL(inflate_kernel, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status);
+  hipLaunchKernelGGL(inflate_kernel<false>, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status, static_cast<int32_t*>(nullptr));
   CGAN_CHECK_LAUNCH("cgan_png_decode (inflate)");
   hipLaunchKernelGGL(unfilter_kernel, dim3(n), dim3(T), 0, s, descs_dev, w, out, status);
   CGAN_CHECK_LAUNCH("cgan_png_decode (unfilter)");
+  return CGAN_OK;
+}
+
+// ---- row-framed files ------------------------------------------------------------------------------------
+namespace {
+
+// The host half of cgan_png_decode_rows: the descriptors as cgan_png_decode checks them, and the candidates' tables one file
+// behind the other.  *max_rows / *cap: the grid's width and the row buffer's bytes.
+int rows_ok(const char* what, const cgan_png_desc* descs, const uint32_t* tables, size_t table_len, int32_t n, size_t blob_bytes,
+            bool with_out, size_t out_bytes, uint32_t* max_rows, uint32_t* cap) {
+  if (const int rc = descs_ok(what, descs, n, blob_bytes, with_out, out_bytes)) return rc;
+  size_t at = 0;
+  *max_rows = 0, *cap = 16;
+  for (int32_t i = 0; i < n; ++i) {
+    const cgan_png_desc& d = descs[i];
+    if (d.rows == 0) continue;
+    CGAN_REQUIRE(tables && at + d.rows + 1 <= table_len, "%s: the table ends before the offsets of file %d", what, i);
+    CGAN_REQUIRE(table_ok(d, tables + at),
+                 "%s: the offsets of file %d do not start behind the zlib header, ascend and stay inside its stream", what, i);
+    at += d.rows + 1;
+    if (d.rows > *max_rows) *max_rows = d.rows;
+    const uint32_t need = (1u + row_bytes(d) + 15u) / 16u * 16u;
+    if (need > *cap) *cap = need;
+  }
+  CGAN_REQUIRE(at == table_len, "%s: a table of %zu words for descriptors whose rows need %zu", what, table_len, at);
+  return CGAN_OK;
+}
+
+}  // namespace
+
+extern "C" int cgan_png_row_table_host(const uint8_t* file, size_t file_bytes, const cgan_png_desc* desc, uint32_t* table) {
+  char why[160] = "";
+  const int rc = host_row_table(file, file_bytes, desc, table, why, sizeof(why));
+  if (rc) cgan_set_error("cgan_png_row_table_host: %s", why);
+  return rc ? CGAN_ERR_BAD_ARG : CGAN_OK;
+}
+
+extern "C" int cgan_png_decode_rows_host(const uint8_t* stream, const cgan_png_desc* desc, const uint32_t* table, uint8_t* inflated,
+                                         uint8_t* pixels, int32_t* status, int32_t* path) {
+  char why[160] = "";
+  const int rc = host_decode_rows(stream, desc, table, inflated, pixels, status, path, why, sizeof(why));
+  if (rc || *status) cgan_set_error("cgan_png_decode_rows_host: %s", why);
+  return rc ? CGAN_ERR_BAD_ARG : CGAN_OK;
+}
+
+extern "C" size_t cgan_png_decode_rows_workspace_bytes(const cgan_png_desc* descs_host, const uint32_t* tables_host, size_t table_len,
+                                                       int32_t n) {
+  uint32_t max_rows, cap;
+  if (rows_ok("cgan_png_decode_rows_workspace_bytes", descs_host, tables_host, table_len, n, ~(size_t)0, false, 0, &max_rows, &cap))
+    return 0;
+  return carve(nullptr, descs_host, n, true).bytes;
+}
+
+extern "C" int cgan_png_decode_rows(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
+                                    const cgan_png_desc* descs_dev, const uint32_t* tables_host, const uint32_t* tables_dev,
+                                    size_t table_len, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status, int32_t* path,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  const char* what = "cgan_png_decode_rows";
+  CGAN_REQUIRE(blob && descs_dev && out && status && path && workspace, "%s: null pointer", what);
+  uint32_t max_rows, cap;
+  if (const int rc = rows_ok(what, descs_host, tables_host, table_len, n, blob_bytes, true, out_bytes, &max_rows, &cap)) return rc;
+  CGAN_REQUIRE(table_len == 0 || tables_dev, "%s: null pointer", what);
+  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(blob) % 4 == 0, "%s: the blob is not 4-byte aligned", what);
+  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(tables_dev) % 4 == 0, "%s: the table is not 4-byte aligned", what);
+  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: the workspace is not 16-byte aligned", what);
+  const Workspace w = carve(workspace, descs_host, n, true);
+  if (w.bytes > workspace_bytes) {
+    cgan_set_error("%s: the workspace has %zu bytes, %zu are needed", what, workspace_bytes, w.bytes);
+    return CGAN_ERR_WORKSPACE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)n, s) != hipSuccess) {
+    cgan_set_error("%s: hipMemsetAsync failed", what);
+    return CGAN_ERR_HIP;
+  }
+  hipLaunchKernelGGL(layout_rows_kernel, dim3(1), dim3(64), 0, s, descs_dev, n, w);
+  CGAN_CHECK_LAUNCH("cgan_png_decode_rows (layout)");
+  if (max_rows) {
+    hipLaunchKernelGGL(inflate_rows_kernel, dim3(max_rows + 1, n), dim3(T), cap, s, blob, descs_dev, tables_dev, (uint32_t)table_len, w,
+                       cap);
+    CGAN_CHECK_LAUNCH("cgan_png_decode_rows (rows)");
+  }
+  hipLaunchKernelGGL(inflate_kernel<true>, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status, path);
+  CGAN_CHECK_LAUNCH("cgan_png_decode_rows (inflate)");
+  hipLaunchKernelGGL(unfilter_kernel, dim3(n), dim3(T), 0, s, descs_dev, w, out, status);
+  CGAN_CHECK_LAUNCH("cgan_png_decode_rows (unfilter)");
   return CGAN_OK;
 }

@@ -6,6 +6,7 @@
 //   Reader           the bit reader: a 64-bit window refilled a word at a time, never a byte outside the stream
 //   Tables           the code tables of the block being decoded: a direct table for short codes, canonical counts behind it
 //   decode_tokens    the inflate step: the stream from where it stands -> a batch of tokens (literal, match, stored run)
+//   Inflate::start_row   the same step on one row's chunk of a row-framed file: the reader bounded to the chunk
 //   unfilter_pixel   the five predictors on up to four bytes at once, selected by the row's filter byte
 //   Adler            the checksum as sums that can be split over rows and added up
 #pragma once
@@ -32,12 +33,21 @@ PNG_HD inline uint32_t bytes_per_pixel(const cgan_png_desc& d) { return (uint32_
 PNG_HD inline uint32_t row_bytes(const cgan_png_desc& d) { return (uint32_t)d.width * bytes_per_pixel(d); }
 PNG_HD inline uint32_t inflated_bytes(const cgan_png_desc& d) { return (uint32_t)d.height * (1u + row_bytes(d)); }   // < 2^29
 PNG_HD inline uint32_t pixel_bytes(const cgan_png_desc& d) { return (uint32_t)d.height * row_bytes(d); }
+PNG_HD inline uint32_t table_words(const cgan_png_desc& d) { return d.rows ? d.rows + 1u : 0u; }       // of a row-framed candidate
 // what the device call and the host twin take: the ranges every index below relies on
 PNG_HD inline bool desc_ok(const cgan_png_desc& d) {
   if (d.width < 1 || d.width > CGAN_PNG_MAX_DIM || d.height < 1 || d.height > CGAN_PNG_MAX_DIM) return false;
   if (!((d.bit_depth == 8 && (d.channels == 1 || d.channels == 3 || d.channels == 4)) || (d.bit_depth == 16 && d.channels == 1)))
     return false;
+  if (d.rows != 0 && d.rows != (uint32_t)d.height) return false;
   return d.stream_bytes >= 2 && d.stream_bytes <= MAX_STREAM_BYTES;
+}
+// a candidate's table: row k's bytes are [table[k], table[k + 1]), the tail's [table[rows], stream_bytes)
+PNG_HD inline bool table_ok(const cgan_png_desc& d, const uint32_t* table) {
+  if (table[0] != 2) return false;
+  for (uint32_t k = 0; k < d.rows; ++k)
+    if (table[k + 1] <= table[k]) return false;
+  return table[d.rows] <= d.stream_bytes;
 }
 
 // ---- the bit reader --------------------------------------------------------------------------------------------------------
@@ -50,6 +60,12 @@ struct Reader {
   uint32_t len, next, n;       // next: the byte the next word starts at, a multiple of 4
   uint64_t win;
   PNG_HD void start(const uint8_t* stream, uint32_t bytes) { p = stream, len = bytes, next = 0, n = 0, win = 0; }
+  // re-seat at byte `at`: at the word that holds the byte, the bits before the byte dropped
+  PNG_HD void seat(uint32_t at) {
+    next = at & ~3u, n = 0, win = 0;
+    refill();
+    take(8 * (at & 3u));
+  }
   PNG_HD uint32_t word() const {
     uint32_t w = 0;
     if (next + 4 <= len) {
@@ -178,9 +194,13 @@ struct Token {
   uint32_t arg;
 };
 constexpr uint32_t PHASE_HEADER = 0, PHASE_CODES = 1, PHASE_STORED = 2, PHASE_TRAILER = 3, PHASE_DONE = 4;
+// MODE_STREAM: a whole zlib stream.  MODE_ROW: one row's chunk of a row-framed file -- whole blocks, none of them final, the
+// last a stored block that ends on the chunk's last byte with the row complete (PHASE_DONE then).  MODE_TAIL: the chunk
+// behind the last row -- blocks that produce nothing up to the final one, then the trailer.
+constexpr uint32_t MODE_STREAM = 0, MODE_ROW = 1, MODE_TAIL = 2;
 struct Inflate {
   Reader r;
-  uint32_t phase, last, stored_left, stored_at;
+  uint32_t phase, last, stored_left, stored_at, mode;
   uint32_t out, limit;         // bytes produced so far; the bytes the image has
   uint32_t adler;              // the trailer, once PHASE_DONE
   uint32_t err;
@@ -189,6 +209,16 @@ struct Inflate {
     r.refill();
     r.take(16);                // the zlib header, checked by the parser
     phase = PHASE_HEADER, last = 0, stored_left = 0, stored_at = 0, out = 0, limit = out_limit, adler = 0, err = 0;
+    mode = MODE_STREAM;
+  }
+  // Row k of a candidate (k = d.rows: the tail): the stream's bytes [begin, end), begin anywhere in a word.  The reader's end is
+  // the chunk's, so nothing behind it is read or taken for a stored run; `out` counts from the row's first byte, so the check
+  // of a match's distance against `out` refuses a match that reaches in front of the row.  begin <= end <= the stream's bytes.
+  PNG_HD void start_row(const uint8_t* stream, uint32_t begin, uint32_t end, uint32_t out_limit, uint32_t row_mode) {
+    r.start(stream, end);
+    r.seat(begin);
+    phase = PHASE_HEADER, last = 0, stored_left = 0, stored_at = 0, out = 0, limit = out_limit, adler = 0, err = 0;
+    mode = row_mode;
   }
 };
 
@@ -283,6 +313,7 @@ PNG_HD inline uint32_t decode_tokens(Inflate& s, Tables& t, Token* tok, uint32_t
   while (nt < max_tok && s.phase != PHASE_DONE && !s.err) {
     if (s.phase == PHASE_HEADER) {
       if (!block_header(s, t) || r.past_end()) s.err = CGAN_PNG_CORRUPT;
+      if (s.mode == MODE_ROW && s.last) s.err = CGAN_PNG_CORRUPT;      // a final block inside a row's chunk
       continue;
     }
     if (s.phase == PHASE_STORED) {
@@ -296,11 +327,13 @@ PNG_HD inline uint32_t decode_tokens(Inflate& s, Tables& t, Token* tok, uint32_t
       }
       // restart the reader behind the run: at the word that holds the byte, the bits before the byte dropped
       const uint32_t at = s.stored_at + s.stored_left;
-      r.next = at & ~3u, r.n = 0, r.win = 0;
-      r.refill();
-      r.take(8 * (at & 3u));
+      r.seat(at);
       s.stored_left = 0;
       s.phase = s.last ? PHASE_TRAILER : PHASE_HEADER;
+      if (s.mode == MODE_ROW && at == r.len) {                         // the row-end rule: the chunk ends with this stored block
+        if (s.out != s.limit) s.err = CGAN_PNG_CORRUPT;
+        s.phase = PHASE_DONE;
+      }
       continue;
     }
     if (s.phase == PHASE_TRAILER) {
@@ -404,13 +437,18 @@ inline uint32_t crc32(const uint8_t* p, size_t n) {
 
 // Walks the chunks.  Returns the status and fills *d for CGAN_PNG_OK; `why` says what was found otherwise.  With dst, the IDAT
 // payloads are copied there one behind the other (at most dst_bytes of them).
-inline int walk(const uint8_t* f, size_t n, cgan_png_desc* d, uint8_t* dst, size_t dst_bytes, char* why, size_t why_len) {
+// Row-framed candidates: exactly height + 1 IDAT chunks, the first longer than the zlib header, chunks
+// 1 .. height - 1 not empty -> d->rows = height, else 0.  With table (height + 1 words), the chunks' cumulative lengths go
+// there: where row k's bytes begin in the stream (row 0: behind the header) and where the tail begins.
+inline int walk(const uint8_t* f, size_t n, cgan_png_desc* d, uint8_t* dst, size_t dst_bytes, char* why, size_t why_len,
+                uint32_t* table = nullptr, uint32_t table_len = 0) {
   static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
   memset(d, 0, sizeof(*d));
   if (n < 8 || memcmp(f, sig, 8) != 0) return snprintf(why, why_len, "not a PNG file"), CGAN_PNG_UNSUPPORTED;
   size_t at = 8;
   bool have_ihdr = false, in_idat = false, idat_over = false, apng = false;
-  uint64_t stream = 0;
+  uint64_t stream = 0, idats = 0;
+  bool framed = true;
   uint8_t head[2] = {0, 0};
   uint32_t depth = 0, colour = 0, interlace = 0, compression = 0, filter = 0, w = 0, h = 0;
   while (at < n) {
@@ -429,6 +467,9 @@ inline int walk(const uint8_t* f, size_t n, cgan_png_desc* d, uint8_t* dst, size
     } else if (is_idat) {
       if (idat_over) return snprintf(why, why_len, "IDAT chunks are not consecutive"), CGAN_PNG_CORRUPT;
       in_idat = true;
+      if (idats == 0 ? len <= 2 : (idats < h && len == 0)) framed = false;
+      if (table && idats < table_len) table[idats] = idats == 0 ? 2u : (uint32_t)(stream < MAX_STREAM_BYTES ? stream : MAX_STREAM_BYTES);
+      ++idats;
       for (uint32_t k = 0; k < len && stream + k < 2; ++k) head[stream + k] = data[k];
       if (dst && len) {
         if (stream + len > dst_bytes) return snprintf(why, why_len, "the stream does not fit"), CGAN_PNG_CORRUPT;
@@ -460,6 +501,7 @@ inline int walk(const uint8_t* f, size_t n, cgan_png_desc* d, uint8_t* dst, size
     return snprintf(why, why_len, "bad zlib header"), CGAN_PNG_CORRUPT;
   d->width = (int32_t)w, d->height = (int32_t)h, d->channels = colour == 0 ? 1 : (colour == 2 ? 3 : 4), d->bit_depth = (int32_t)depth;
   d->stream_bytes = (uint32_t)stream;
+  d->rows = (framed && idats == (uint64_t)h + 1) ? h : 0;
   return CGAN_PNG_OK;
 }
 

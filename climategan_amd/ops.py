@@ -815,6 +815,42 @@ def png_decode(blob: torch.Tensor, descs, descs_dev: torch.Tensor):
     return out, status
 
 
+PNG_PATH_SERIAL, PNG_PATH_ROWS, PNG_PATH_REFUSED = 0, 1, 2      # how a file of png_decode_rows was inflated
+
+
+def png_decode_rows(blob: torch.Tensor, descs, descs_dev: torch.Tensor, tables, tables_dev):
+    """``png_decode`` with the row path -> (out, status, path).  ``tables``: a ctypes ``c_uint32`` array with
+    the row offsets of every candidate (``descs[i].rows != 0``; ``cgan_png_row_table_host``) one file behind the other,
+    ``tables_dev``: the same words as an int32 device tensor (both may be None where the batch has no candidate).  Every row of
+    a candidate is inflated by a wave of its own; a candidate whose rows do not satisfy the row rule and every other file go
+    through the serial kernel in the same call.  ``path``: int32 [N] device tensor, PNG_PATH_SERIAL, PNG_PATH_ROWS or
+    PNG_PATH_REFUSED (serial after the row path refused).  Nothing is synchronised."""
+    _need_cuda(blob, descs_dev)
+    n = len(descs)
+    words = len(tables) if tables is not None else 0
+    if blob.dtype != torch.uint8 or descs_dev.dtype != torch.uint8 or not blob.is_contiguous() or not descs_dev.is_contiguous():
+        raise RuntimeError("png_decode_rows: contiguous uint8 tensors expected")
+    if n < 1 or descs_dev.numel() != n * C.sizeof(_lib.PngDesc):
+        raise RuntimeError("png_decode_rows: %d descriptors on the host, %d bytes of them on the device" % (n, descs_dev.numel()))
+    if words:
+        _need_cuda(tables_dev)
+        if tables_dev.dtype != torch.int32 or not tables_dev.is_contiguous() or tables_dev.numel() != words:
+            raise RuntimeError("png_decode_rows: %d table words on the host, the device's are not the same contiguous int32 words" % words)
+    lib = _lib.load()
+    tables_host = C.addressof(tables) if words else None
+    nbytes = _size(lib.cgan_png_decode_rows_workspace_bytes(C.addressof(descs), tables_host, words, n),
+                   "cgan_png_decode_rows_workspace_bytes")
+    ws = _empty(nbytes, dtype=torch.uint8, device=blob.device)
+    status = _empty((n,), dtype=torch.int32, device=blob.device)
+    path = _empty((n,), dtype=torch.int32, device=blob.device)
+    out = _empty((max(d.out_offset + d.width * d.height * d.channels * (d.bit_depth // 8) for d in descs),), dtype=torch.uint8,
+                 device=blob.device)
+    _lib.check(lib.cgan_png_decode_rows(_ptr(blob), blob.numel(), C.addressof(descs), _ptr(descs_dev), tables_host,
+                                        _ptr(tables_dev) if words else None, words, n, _ptr(out), out.numel(), _ptr(status),
+                                        _ptr(path), _ptr(ws), nbytes, _stream()), "cgan_png_decode_rows")
+    return out, status, path
+
+
 def smog(x: torch.Tensor, depth: NHWC, airlight: float, beta: float, alpha: float, yellow_rgb01) -> torch.Tensor:
     """Smog event (reference trainer.py:1879-1939): x NCHW fp32 in [-1, 1], depth the decoder's 1-channel NHWC map;
     returns the smogged image, NCHW fp32."""

@@ -3,7 +3,9 @@
 host encoder behind it: a CPU tensor is refused.
 
 The other way: ``probe`` reads a file's chunks on the host, ``decode`` uploads a batch of files' zlib streams
-and inflates and unfilters them on the device (``ops.png_decode``), one wave per file.
+and inflates and unfilters them on the device (``ops.png_decode``), one wave per file.  Row-framed files (one
+IDAT chunk per row, as ``encode`` writes them; ``probe`` reports them as ``rows == height``) are inflated one wave per row
+(``ops.png_decode_rows``); ``python -m climategan_amd.repack_png`` turns a folder's PNG files into such files.
 """
 import ctypes as C
 from pathlib import Path
@@ -28,7 +30,8 @@ def write(img_u8, paths, level=1):
 
 def probe(data):
     """The bytes of one file -> (descriptor, None) if the device decoder takes it (a ``_lib.PngDesc``: width, height,
-    channels, bit depth, the length of its zlib stream), else (None, reason): not a PNG file, a kind of PNG outside DESIGN
+    channels, bit depth, the length of its zlib stream, and ``rows``: the height if the IDAT chunks make the file a row-framed
+    candidate, DESIGN 4.22, else 0), else (None, reason): not a PNG file, a kind of PNG outside DESIGN
     4.21's list (interlaced, palette, grey + alpha, fewer than 8 bits, 16-bit colour, animated), or broken chunks.  Host
     only."""
     data = bytes(data)
@@ -68,6 +71,21 @@ def upload(descs_and_data, device):
             torch.frombuffer(bytearray(descs), dtype=torch.uint8).to(device))
 
 
+def row_tables(descs, datas, device):
+    """The row offsets of a batch's candidates (``descs[k].rows != 0``; ``datas[k]``: that file's bytes) as
+    ``ops.png_decode_rows`` takes them -> (tables, tables_dev): one ``c_uint32`` array, every candidate's rows + 1 words one
+    file behind the other, and the same words uploaded; (None, None) without a candidate."""
+    words = sum(d.rows + 1 for d in descs if d.rows)
+    if not words:
+        return None, None
+    tables, at, lib = (C.c_uint32 * words)(), 0, _lib.load()
+    for d, data in zip(descs, datas):
+        if d.rows:
+            _lib.check(lib.cgan_png_row_table_host(data, len(data), C.addressof(d), C.byref(tables, 4 * at)), "cgan_png_row_table_host")
+            at += d.rows + 1
+    return tables, torch.frombuffer(bytearray(tables), dtype=torch.int32).to(device)
+
+
 def try_decode(files, device="cuda"):
     """``decode`` without raising for a file's sake -> (images, reasons): ``images[i]`` is None for a file that was not
     decoded and ``reasons[i]`` says why."""
@@ -84,7 +102,11 @@ def try_decode(files, device="cuda"):
             taken.append((i, d))
     if taken:
         blob, descs, descs_dev = upload([(d, datas[i]) for i, d in taken], device)
-        out, status = ops.png_decode(blob, descs, descs_dev)
+        if any(d.rows for d in descs):                                        # row-framed files: one wave per row
+            tables, tables_dev = row_tables(descs, [datas[i] for i, _ in taken], device)
+            out, status, _ = ops.png_decode_rows(blob, descs, descs_dev, tables, tables_dev)
+        else:
+            out, status = ops.png_decode(blob, descs, descs_dev)
         for (i, _), d, s in zip(taken, descs, status.tolist()):               # the one wait
             if s != ops.PNG_OK:
                 reasons[i] = STATUS_TEXT[ops.PNG_CORRUPT]
@@ -99,7 +121,8 @@ def try_decode(files, device="cuda"):
 def decode(files, fallback=False, device="cuda"):
     """``files``: a list of ``bytes`` or paths of PNG files -> a list of device tensors, views into one allocation: uint8
     [H, W, C] with C = 1, 3 or 4, and ``torch.uint16`` [H, W, 1] for 16-bit grey.  One upload of the bytes, one of the
-    descriptors, one wait (for the status words).  A file the decoder does not take (``probe``) or reports as corrupt raises
+    descriptors, one wait (for the status words); a batch that holds a row-framed file uploads its row offsets
+    too and goes through ``ops.png_decode_rows``.  A file the decoder does not take (``probe``) or reports as corrupt raises
     ``RuntimeError`` with its index and the reason -- unless ``fallback``: that file is then decoded by PIL on the host and
     uploaded."""
     images, reasons = try_decode(files, device)

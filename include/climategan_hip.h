@@ -757,12 +757,13 @@ int cgan_jpeg_decode_coefficients(const uint8_t* blob, size_t blob_bytes, const 
 #define CGAN_PNG_CORRUPT 2
 #define CGAN_PNG_MAX_DIM 8192
 /* One file, as cgan_png_parse_host fills it.  channels: 1, 3 or 4; bit_depth: 8, or 16 (channels = 1 only); stream_bytes: the
- * IDAT payloads together, one zlib stream.  blob_offset / out_offset are the caller's: where the file's zlib stream (as
+ * IDAT payloads together, one zlib stream; rows: the height if the chunks make the file a row-framed candidate (below), else
+ * 0.  blob_offset / out_offset are the caller's: where the file's zlib stream (as
  * cgan_png_stream_host copies it; a multiple of 4) stands in the input blob and where its first pixel goes in the output
  * blob of the device call (a multiple of 2 for 16-bit files). */
 typedef struct cgan_png_desc {
   int32_t width, height, channels, bit_depth;
-  uint32_t stream_bytes, reserved;
+  uint32_t stream_bytes, rows;
   int64_t blob_offset, out_offset;
 } cgan_png_desc;
 /* Host only.  cgan_png_parse_host: the bytes of one file -> *desc and *status (OK, UNSUPPORTED or CORRUPT; the reason in
@@ -783,6 +784,30 @@ size_t cgan_png_decode_workspace_bytes(const cgan_png_desc* descs_host, int32_t 
 int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host, const cgan_png_desc* descs_dev,
                     int32_t n, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
                     void* stream);
+/* Row-framed files: a file with exactly height + 1 IDAT chunks, the first longer than the zlib header and chunks
+ * 1 .. height - 1 not empty, is a candidate, and cgan_png_parse_host sets desc->rows = height for it (0 otherwise).  Such files
+ * are what cgan_png_encode_u8 writes: one chunk per row, every row coded on its own and ended by a stored block on the chunk's
+ * last byte, then a chunk with the final block and the Adler-32.
+ * cgan_png_row_table_host (host only): a candidate's rows + 1 stream offsets, the IDAT chunks' cumulative lengths: table[k] is
+ * where row k's bytes begin in the zlib stream (table[0] = 2, behind the header) and table[rows] where the tail begins.
+ * cgan_png_decode_rows: cgan_png_decode with a second inflate path.  tables_host / tables_dev: the candidates' tables one
+ * behind the other in the files' order, table_len words in all, in host and in device memory (0 words: both may be null).
+ * Every row of a candidate is inflated by a wave of its own, which holds it to the row rule: whole blocks from the table's
+ * offset, none final, exactly 1 + row bytes produced, no match reaching in front of the row, the last block a stored one that
+ * ends on the chunk's last byte; the tail: blocks that produce nothing, the last final, the trailer.  A candidate with a row
+ * that fails is decoded by the serial kernel in the same call, like every file that is no candidate, and the serial verdict
+ * stands; the row path itself never reports CORRUPT.  path: n device words, 0 = serial, 1 = rows, 2 = serial after the row
+ * path refused.  One memset and four launches, nothing synchronised.  Refused before any launch (CGAN_ERR_BAD_ARG), by the
+ * size query too (0): what cgan_png_decode refuses, rows that is neither 0 nor the height, a table that does not begin with 2,
+ * does not ascend, leaves the stream or does not have exactly the candidates' rows + 1 words.
+ * cgan_png_decode_rows_host: the same path serially (host only): the core's functions row by row, then the fallback. */
+int cgan_png_row_table_host(const uint8_t* file, size_t file_bytes, const cgan_png_desc* desc, uint32_t* table);
+int cgan_png_decode_rows_host(const uint8_t* stream, const cgan_png_desc* desc, const uint32_t* table, uint8_t* inflated,
+                              uint8_t* pixels, int32_t* status, int32_t* path);
+size_t cgan_png_decode_rows_workspace_bytes(const cgan_png_desc* descs_host, const uint32_t* tables_host, size_t table_len, int32_t n);
+int cgan_png_decode_rows(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host, const cgan_png_desc* descs_dev,
+                         const uint32_t* tables_host, const uint32_t* tables_dev, size_t table_len, int32_t n, uint8_t* out,
+                         size_t out_bytes, int32_t* status, int32_t* path, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Smog event (Trainer.compute_smog, climategan/trainer.py:1879-1939, parameters shared/trainer/events.yaml:9-14):
  * irradiance = srgb2lrgb(normalize(x)) (tutils.py:534-538), depth = normalize(1 / normalize(d, 0.3, 1), 0.1, 1)
