@@ -299,6 +299,8 @@ _SIGNATURES = {
     "cgan_png_decode_rows_workspace_bytes": (C.c_size_t, [_P, _P, C.c_size_t, C.c_int32]),
     "cgan_png_decode_rows": (C.c_int, [_P, C.c_size_t, _P, _P, _P, _P, C.c_size_t, C.c_int32, _P, C.c_size_t, _P, _P, _P,
                                        C.c_size_t, _P]),
+    "cgan_png_unfilter_wide_params": (None, [_P, _P, _P]),
+    "cgan_png_unfilter_wide_host": (C.c_int, [_P, _P, C.c_uint32, C.c_int32, C.c_int32, _P, _P]),
     "cgan_smog_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "cgan_smog_nchw": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), _P, C.c_size_t, _P]),

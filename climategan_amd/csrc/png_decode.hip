@@ -12,9 +12,10 @@
 //                    ring, which is all a match ever reads; the workspace is only written.  Nothing is written to the ring
 //                    ahead of its turn: a byte written early would take the slot of the byte 32 KiB before it, which a match
 //                    still to come may read.  Leaves the stream's Adler-32 trailer.
-//   unfilter_kernel  one wave per file, 64 rows at a time as a skewed wavefront: lane r is at pixel t - r in step t, its left
-//                    neighbour is its own last result, the two pixels above come from lane r - 1 by __shfl_up; lane 0 reads
-//                    the previous group's last row from LDS, where lane 63 left it.  Sums the Adler-32 of the bytes it reads
+//   unfilter_kernel  one workgroup of UNFILTER_WAVES waves per file, 64 rows per wave at a time as one skewed
+//                    wavefront across the waves: lane r of a wave is at pixel t - r in the wave's step t, its left neighbour
+//                    is its own last result, the two pixels above come from lane r - 1 by __shfl_up; lane 0 reads the row
+//                    above from LDS, where lane 63 of the wave before left it.  Sums the Adler-32 of the bytes it reads
 //                    anyway, row by row, and compares it with the trailer.  Writes the tight pixels.
 // Launches and memsets per call: 1 memset (status) + layout + inflate + unfilter = 4.
 //
@@ -33,9 +34,10 @@
 // Bounds: the reader never touches a byte outside [stream, stream + stream_bytes) (Reader::word); decode_tokens hands out a
 // token only if its bytes end inside the file's inflated extent and its source starts at or behind the output's start; a
 // stored run's source is checked against the stream's end.  Loops: a round of inflate_kernel either brings 64 tokens, each of
-// which consumed a bit, or is the last; the copies are bounded by a token's length, the wavefront by the image's size.  No wave
-// waits for another: the only barriers are __syncthreads() of a one-wave workgroup, reached by all lanes (every branch around
-// them depends on values all lanes share).
+// which consumed a bit, or is the last; the copies are bounded by a token's length, the wavefront by the image's size.  In the
+// inflate kernels no wave waits for another: their barriers are __syncthreads() of a one-wave workgroup, reached by all lanes
+// (every branch around them depends on values all lanes share).  The unfilter's waves do wait for each other, at barriers
+// whose number comes from the descriptor alone (see unfilter_kernel).
 #include "cgan_common.h"
 #include "png_decode_host.h"
 
@@ -45,7 +47,13 @@ using namespace png_dec;
 
 constexpr int T = 64;                         // one wave
 constexpr uint32_t BATCH = 64;                // tokens per round: one per lane
-constexpr int PREFETCH = 8;                   // steps of the wavefront whose bytes are loaded together
+// the unfilter's workgroup: waves per file -- chosen from 4, 8 and 16 by measurement -- and the steps a wave
+// runs behind its predecessor beyond the 64 that its rows lie lower
+#ifndef CGAN_PNG_UNFILTER_WAVES
+#define CGAN_PNG_UNFILTER_WAVES 16
+#endif
+constexpr int UNFILTER_WAVES = CGAN_PNG_UNFILTER_WAVES;
+constexpr int UNFILTER_LAG = UNF_PREFETCH;
 
 struct Workspace {
   uint64_t* layout;                           // per file: where its inflated bytes start in `inflated`
@@ -274,62 +282,89 @@ __global__ __launch_bounds__(T) void inflate_kernel(const uint8_t* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(T) void unfilter_kernel(const cgan_png_desc* __restrict__ descs, Workspace w, uint8_t* __restrict__ out_base,
-                                                     int32_t* __restrict__ status) {
-  __shared__ uint32_t above[CGAN_PNG_MAX_DIM];          // the last row of the group before, a pixel per word
+// One workgroup of NW waves per file (the schedule is png_decode_core.h's unf_* functions, which the host twin
+// host_unfilter_wide runs step by step).  Inside a wave: a skewed wavefront, lane r at pixel t - r in the wave's step t, the left
+// neighbour its own last result, the two pixels above from lane r - 1 by __shfl_up.  Between waves: wave j runs j * (64 + LAG)
+// steps behind wave 0; its lane 0 reads the row above from ring[j], where lane 63 of wave j - 1 wrote it LAG + 1 steps -- at
+// least one barrier -- earlier.  Between passes: lane 63 of the last wave leaves its row in `above` for wave 0.
+// Every loop around a barrier counts chunks and passes, which come from the descriptor: all waves and lanes make the same
+// turns, and those with no row or no pixel only skip the memory accesses.  The one early return is the same in every thread.
+template <int NW, int LAG>
+__global__ __launch_bounds__(T * NW) void unfilter_kernel(const cgan_png_desc* __restrict__ descs, Workspace w,
+                                                          uint8_t* __restrict__ out_base, int32_t* __restrict__ status) {
+  static_assert(NW >= 1 && NW <= UNF_MAX_WAVES && LAG >= UNF_PREFETCH && LAG % UNF_PREFETCH == 0, "see unf_params_ok");
+  constexpr uint32_t RING = unf_ring_words(LAG);
+  __shared__ uint32_t above[CGAN_PNG_MAX_DIM];          // the last row of the pass before, a pixel per word
+  __shared__ uint32_t ring[NW][RING];                   // ring[j]: the last row of wave j - 1, the pixels wave j reads next
+  __shared__ uint32_t sums[NW][3];                      // per wave: the Adler sums of its rows, whether a filter byte was bad
+  __shared__ int32_t skip;
   const int file = blockIdx.x;
-  const int lane = threadIdx.x;
-  if (status[file] != 0) return;                        // the whole wave: the inflate failed, there is nothing to unfilter
+  const int wave = threadIdx.x / T, lane = threadIdx.x % T;
+  if (threadIdx.x == 0) skip = status[file];
+  __syncthreads();
+  if (skip != 0) return;                                // every thread: the inflate failed, there is nothing to unfilter
   const cgan_png_desc d = descs[file];
   const int W = d.width, H = d.height;
   const uint32_t bpp = bytes_per_pixel(d), rb = row_bytes(d), total = inflated_bytes(d);
   const bool swap = d.bit_depth == 16;
   const uint8_t* in = w.inflated + w.layout[file];
   uint8_t* out = out_base + d.out_offset;
+  const uint32_t passes = unf_passes(H, NW), chunks = unf_chunks(W, NW, LAG);
+  const int behind = unf_wave_offset(wave, LAG);
   Adler ad;
   ad.start();
   bool bad = false;
-  for (int g = 0; g * T < H; ++g) {
-    const int y = g * T + lane;
+  for (uint32_t p = 0; p < passes; ++p) {
+    const int y = unf_row(p, wave, lane, NW);
     const bool live = y < H;
     const uint8_t* row = in + (size_t)(live ? y : 0) * (1 + rb);
     const uint32_t filter = live ? row[0] : 0u;
     if (live) ad.byte(filter);
     bad = bad || filter > 4;
     uint32_t cur = 0, prev = 0, above_left = 0;         // my results of the last step and the one before; lane 0: its last b
-    for (int t0 = 0; t0 < W + T - 1; t0 += PREFETCH) {
-      uint32_t raw[PREFETCH];
+    for (uint32_t c = 0; c < chunks; ++c) {
+      const int t0 = (int)(c * UNF_PREFETCH) - behind;
+      if (!unf_wave_idle(unf_row(p, wave, 0, NW), H, t0, W)) {             // the same in every lane of the wave; no barrier inside
+        uint32_t raw[UNF_PREFETCH];
 #pragma unroll
-      for (int u = 0; u < PREFETCH; ++u) {
-        const int x = t0 + u - lane;
-        raw[u] = 0;
-        if (live && x >= 0 && x < W)
-          for (uint32_t k = 0; k < bpp; ++k) raw[u] |= (uint32_t)row[1 + (uint32_t)x * bpp + k] << (8 * k);
-      }
-#pragma unroll
-      for (int u = 0; u < PREFETCH; ++u) {
-        const int x = t0 + u - lane;
-        const bool active = live && x >= 0 && x < W;
-        uint32_t b = __shfl_up(cur, 1), c = __shfl_up(prev, 1);
-        if (lane == 0) {
-          c = above_left;
-          b = (g > 0 && x < W) ? above[x & (CGAN_PNG_MAX_DIM - 1)] : 0u;
-          above_left = b;
+        for (int u = 0; u < UNF_PREFETCH; ++u) {
+          const int x = t0 + u - lane;
+          raw[u] = 0;
+          if (live && x >= 0 && x < W)
+            for (uint32_t k = 0; k < bpp; ++k) raw[u] |= (uint32_t)row[1 + (uint32_t)x * bpp + k] << (8 * k);
         }
-        const uint32_t v = active ? unfilter_pixel(filter, raw[u], cur, b, c) : 0u;
-        if (active) {
-          uint8_t* px = out + ((size_t)y * W + x) * bpp;
-          for (uint32_t k = 0; k < bpp; ++k) {
-            px[swap ? 1 - k : k] = (uint8_t)(v >> (8 * k));
-            ad.byte((raw[u] >> (8 * k)) & 255u);
+#pragma unroll
+        for (int u = 0; u < UNF_PREFETCH; ++u) {
+          const int x = t0 + u - lane;
+          const bool active = live && x >= 0 && x < W;
+          uint32_t b = __shfl_up(cur, 1), cc = __shfl_up(prev, 1);
+          if (lane == 0) {
+            cc = above_left;
+            b = 0u;
+            if (active) {
+              if (wave > 0) b = ring[wave][unf_ring_index(x, RING)];
+              else if (p > 0) b = above[unf_above_index(x)];
+            }
+            above_left = b;
           }
-          if (lane == T - 1) above[x & (CGAN_PNG_MAX_DIM - 1)] = v;
+          const uint32_t v = active ? unfilter_pixel(filter, raw[u], cur, b, cc) : 0u;
+          if (active) {
+            uint8_t* px = out + ((size_t)y * W + x) * bpp;
+            for (uint32_t k = 0; k < bpp; ++k) {
+              px[swap ? 1 - k : k] = (uint8_t)(v >> (8 * k));
+              ad.byte((raw[u] >> (8 * k)) & 255u);
+            }
+            if (lane == T - 1) {
+              if (wave + 1 < NW) ring[(wave + 1) % NW][unf_ring_index(x, RING)] = v;
+              else above[unf_above_index(x)] = v;
+            }
+          }
+          prev = cur, cur = v;
         }
-        prev = cur, cur = v;
       }
+      __syncthreads();                                  // chunks * passes of them, whatever the wave and the lane
     }
     if (live) ad.end_piece(total - (uint32_t)(y + 1) * (1 + rb));
-    __syncthreads();
   }
   uint32_t s1 = ad.s1, s2 = ad.s2;
   for (int off = 1; off < T; off <<= 1) {
@@ -337,7 +372,22 @@ __global__ __launch_bounds__(T) void unfilter_kernel(const cgan_png_desc* __rest
     s2 = (s2 + __shfl_xor(s2, off)) % ADLER_MOD;
   }
   const bool any_bad = __ballot(bad) != 0;
-  if (lane == 0 && (any_bad || adler_value(s1, s2, total) != w.adler[file])) atomicOr(&status[file], (int32_t)CGAN_PNG_CORRUPT);
+  if (lane == 0) sums[wave][0] = s1, sums[wave][1] = s2, sums[wave][2] = any_bad ? 1u : 0u;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t flag = 0;
+    s1 = 0, s2 = 0;
+    for (int j = 0; j < NW; ++j) {
+      s1 = (s1 + sums[j][0]) % ADLER_MOD;
+      s2 = (s2 + sums[j][1]) % ADLER_MOD;
+      flag |= sums[j][2];
+    }
+    if (flag || adler_value(s1, s2, total) != w.adler[file]) atomicOr(&status[file], (int32_t)CGAN_PNG_CORRUPT);
+  }
+}
+
+void launch_unfilter(int32_t n, hipStream_t s, const cgan_png_desc* descs_dev, const Workspace& w, uint8_t* out, int32_t* status) {
+  hipLaunchKernelGGL((unfilter_kernel<UNFILTER_WAVES, UNFILTER_LAG>), dim3(n), dim3(T * UNFILTER_WAVES), 0, s, descs_dev, w, out, status);
 }
 
 int descs_ok(const char* what, const cgan_png_desc* descs, int32_t n, size_t blob_bytes, bool with_out, size_t out_bytes) {
@@ -381,6 +431,24 @@ extern "C" int cgan_png_decode_host(const uint8_t* stream, const cgan_png_desc* 
   return rc ? CGAN_ERR_BAD_ARG : CGAN_OK;
 }
 
+extern "C" void cgan_png_unfilter_wide_params(int32_t* waves, int32_t* lag, int32_t* prefetch) {
+  if (waves) *waves = UNFILTER_WAVES;
+  if (lag) *lag = UNFILTER_LAG;
+  if (prefetch) *prefetch = UNF_PREFETCH;
+}
+
+extern "C" int cgan_png_unfilter_wide_host(const cgan_png_desc* desc, const uint8_t* inflated, uint32_t trailer, int32_t waves,
+                                           int32_t lag, uint8_t* pixels, int32_t* status) {
+  char why[160] = "";
+  if (!desc) {
+    cgan_set_error("cgan_png_unfilter_wide_host: null pointer");
+    return CGAN_ERR_BAD_ARG;
+  }
+  const int rc = host_unfilter_wide(*desc, inflated, trailer, waves, lag, pixels, status, why, sizeof(why));
+  if (rc || *status) cgan_set_error("cgan_png_unfilter_wide_host: %s", why);
+  return rc == 0 ? CGAN_OK : (rc == -2 ? CGAN_ERR_INTERNAL : CGAN_ERR_BAD_ARG);
+}
+
 extern "C" size_t cgan_png_decode_workspace_bytes(const cgan_png_desc* descs_host, int32_t n) {
   if (descs_ok("cgan_png_decode_workspace_bytes", descs_host, n, ~(size_t)0, false, 0)) return 0;
   return carve(nullptr, descs_host, n).bytes;
@@ -408,7 +476,7 @@ extern "C" int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cga
   CGAN_CHECK_LAUNCH("cgan_png_decode (layout)");
   hipLaunchKernelGGL(inflate_kernel<false>, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status, static_cast<int32_t*>(nullptr));
   CGAN_CHECK_LAUNCH("cgan_png_decode (inflate)");
-  hipLaunchKernelGGL(unfilter_kernel, dim3(n), dim3(T), 0, s, descs_dev, w, out, status);
+  launch_unfilter(n, s, descs_dev, w, out, status);
   CGAN_CHECK_LAUNCH("cgan_png_decode (unfilter)");
   return CGAN_OK;
 }
@@ -494,7 +562,7 @@ extern "C" int cgan_png_decode_rows(const uint8_t* blob, size_t blob_bytes, cons
   }
   hipLaunchKernelGGL(inflate_kernel<true>, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status, path);
   CGAN_CHECK_LAUNCH("cgan_png_decode_rows (inflate)");
-  hipLaunchKernelGGL(unfilter_kernel, dim3(n), dim3(T), 0, s, descs_dev, w, out, status);
+  launch_unfilter(n, s, descs_dev, w, out, status);
   CGAN_CHECK_LAUNCH("cgan_png_decode_rows (unfilter)");
   return CGAN_OK;
 }

@@ -404,6 +404,38 @@ PNG_HD inline uint32_t unfilter_pixel(uint32_t filter, uint32_t raw, uint32_t a,
   return out;
 }
 
+// ---- the wide unfilter's schedule ------------------------------------------------------------------------------
+// One workgroup of `waves` waves per file.  In pass p, wave j, lane r owns row p * 64 * waves + 64 * j + r; in step s of a pass
+// that lane is at pixel s - unf_wave_offset(j) - r.  Lane 0 of wave j > 0 reads the row above it from a ring that lane 63 of
+// wave j - 1 wrote unf lag + 1 steps earlier: lag is a multiple of UNF_PREFETCH and at least that, so the write lies in an
+// earlier chunk of UNF_PREFETCH steps -- in front of the barrier that ends it -- and a ring of at least lag + 1 + UNF_PREFETCH
+// words is not written again before the chunk of the read is over.  Every count below depends on the descriptor alone.
+constexpr int UNF_LANES = 64;                        // one wave
+constexpr int UNF_PREFETCH = 8;                      // steps of the wavefront between two barriers; their bytes are loaded together
+constexpr int UNF_MAX_WAVES = 16;
+PNG_HD inline bool unf_params_ok(int waves, int lag) {
+  return waves >= 1 && waves <= UNF_MAX_WAVES && lag >= UNF_PREFETCH && lag % UNF_PREFETCH == 0 && lag <= 8 * UNF_PREFETCH;
+}
+PNG_HD inline int unf_wave_offset(int wave, int lag) { return wave * (UNF_LANES + lag); }   // steps wave `wave` runs behind wave 0
+PNG_HD inline uint32_t unf_steps(int width, int waves, int lag) {
+  return (uint32_t)(width + UNF_LANES - 1 + unf_wave_offset(waves - 1, lag));
+}
+PNG_HD inline uint32_t unf_chunks(int width, int waves, int lag) { return (unf_steps(width, waves, lag) + UNF_PREFETCH - 1) / UNF_PREFETCH; }
+PNG_HD inline uint32_t unf_passes(int height, int waves) { return ((uint32_t)height + UNF_LANES * waves - 1) / (uint32_t)(UNF_LANES * waves); }
+PNG_HD inline int unf_row(uint32_t pass, int wave, int lane, int waves) { return (int)pass * UNF_LANES * waves + UNF_LANES * wave + lane; }
+PNG_HD constexpr uint32_t unf_ring_words(int lag) {                                          // a power of two
+  uint32_t n = 1;
+  while (n < (uint32_t)(lag + 1 + UNF_PREFETCH)) n <<= 1;
+  return n;
+}
+PNG_HD inline uint32_t unf_ring_index(int x, uint32_t words) { return (uint32_t)x & (words - 1u); }
+PNG_HD inline uint32_t unf_above_index(int x) { return (uint32_t)x & (uint32_t)(CGAN_PNG_MAX_DIM - 1); }
+// whether a wave has nothing to do in the chunk whose first step is t0 of its own clock: its rows lie beyond the image, or
+// its lanes are all in front of the row's first pixel or behind its last.  The same in every lane of the wave.
+PNG_HD inline bool unf_wave_idle(int first_row, int height, int t0, int width) {
+  return first_row >= height || t0 + UNF_PREFETCH - 1 < 0 || t0 - (UNF_LANES - 1) >= width;
+}
+
 // ---- Adler-32 --------------------------------------------------------------------------------------------------------------
 // adler = (s2 << 16) | s1 with s1 = 1 + sum of the bytes, s2 = N + sum over i of (N - i) * byte i, both mod 65521: linear in
 // the bytes, so a piece of the stream (a row) contributes on its own and the contributions add up in any order.

@@ -87,6 +87,129 @@ inline int host_unfilter(const cgan_png_desc& d, const uint8_t* inflated, uint32
   return 0;
 }
 
+// The wide unfilter kernel's schedule run on the host: pass by pass, chunk by chunk, wave by wave, step by step,
+// lane by lane, with the core's unf_* functions for every index, as unfilter_kernel<waves, lag> does.  What a barrier orders
+// on the device is checked here: every ring and `above` slot carries the pixel it holds and the chunk that wrote it, and a
+// read that finds another pixel (never written, or written again already) or a write of the same chunk (no barrier between
+// the waves) is a violation: -2, the reason in `why`.  -1: an argument refused.  The status as host_unfilter sets it.
+inline int host_unfilter_wide(const cgan_png_desc& d, const uint8_t* inflated, uint32_t trailer, int waves, int lag, uint8_t* pixels,
+                              int32_t* status, char* why, size_t why_len) {
+  if (!inflated || !pixels || !status) return snprintf(why, why_len, "null pointer"), -1;
+  if (!desc_ok(d)) return snprintf(why, why_len, "not a descriptor the parser produces"), -1;
+  if (!unf_params_ok(waves, lag))
+    return snprintf(why, why_len, "waves = %d, lag = %d: 1 .. %d waves and a lag that is a multiple of %d, %d .. %d, expected", waves, lag,
+                    UNF_MAX_WAVES, UNF_PREFETCH, UNF_PREFETCH, 8 * UNF_PREFETCH), -1;
+  struct Slot {
+    uint32_t v;
+    int64_t pixel, chunk;      // which pixel of which pass (pass * MAX_DIM + x), written in which chunk (counted over the passes)
+  };
+  struct Lane {
+    uint32_t cur, prev, above_left, filter;
+    Adler ad;
+    bool bad;
+  };
+  const int W = d.width, H = d.height, L = UNF_LANES;
+  const uint32_t bpp = bytes_per_pixel(d), rb = row_bytes(d), total = inflated_bytes(d), ring_words = unf_ring_words(lag);
+  const bool swap = d.bit_depth == 16;
+  const uint32_t passes = unf_passes(H, waves), chunks = unf_chunks(W, waves, lag);
+  Slot* above = new Slot[CGAN_PNG_MAX_DIM];
+  Slot* ring = new Slot[(size_t)waves * ring_words];
+  Lane* lanes = new Lane[(size_t)waves * L];
+  uint32_t* shifted = new uint32_t[2 * L];                 // what __shfl_up hands every lane: the values of the step before
+  for (int i = 0; i < CGAN_PNG_MAX_DIM; ++i) above[i] = Slot{0, -1, -1};
+  for (size_t i = 0; i < (size_t)waves * ring_words; ++i) ring[i] = Slot{0, -1, -1};
+  for (int i = 0; i < waves * L; ++i) {
+    lanes[i].ad.start();
+    lanes[i].bad = false;
+  }
+  int rc = 0;
+  auto read_slot = [&](const Slot& s, int64_t pixel, int64_t chunk, const char* what, int wave, int x) -> uint32_t {
+    if (rc == 0 && s.pixel != pixel)
+      rc = (snprintf(why, why_len, "wave %d reads pixel %d of %s, which %s", wave, x, what, s.pixel < 0 ? "was never written" : "holds another pixel"), -2);
+    else if (rc == 0 && s.chunk >= chunk)
+      rc = (snprintf(why, why_len, "wave %d reads pixel %d of %s in the chunk that wrote it", wave, x, what), -2);
+    return s.v;
+  };
+  for (uint32_t p = 0; p < passes && rc == 0; ++p) {
+    for (int j = 0; j < waves; ++j)
+      for (int r = 0; r < L; ++r) {
+        Lane& l = lanes[j * L + r];
+        const int y = unf_row(p, j, r, waves);
+        l.filter = y < H ? inflated[(size_t)y * (1 + rb)] : 0u;
+        if (y < H) l.ad.byte(l.filter);
+        l.bad = l.bad || l.filter > 4;
+        l.cur = l.prev = l.above_left = 0;
+      }
+    for (uint32_t c = 0; c < chunks && rc == 0; ++c) {
+      const int64_t chunk = (int64_t)p * chunks + c;
+      for (int j = 0; j < waves; ++j) {
+        const int t0 = (int)(c * UNF_PREFETCH) - unf_wave_offset(j, lag);
+        if (unf_wave_idle(unf_row(p, j, 0, waves), H, t0, W)) continue;
+        for (int u = 0; u < UNF_PREFETCH; ++u) {
+          for (int r = 0; r < L; ++r) shifted[r] = lanes[j * L + r].cur, shifted[L + r] = lanes[j * L + r].prev;
+          for (int r = 0; r < L; ++r) {
+            Lane& l = lanes[j * L + r];
+            const int y = unf_row(p, j, r, waves), x = t0 + u - r;
+            const bool live = y < H, active = live && x >= 0 && x < W;
+            uint32_t b = r ? shifted[r - 1] : 0u, cc = r ? shifted[L + r - 1] : 0u;
+            if (r == 0) {
+              cc = l.above_left;
+              b = 0u;
+              if (active) {
+                const int64_t pixel = (int64_t)p * CGAN_PNG_MAX_DIM + x;
+                if (j > 0) {
+                  b = read_slot(ring[(size_t)j * ring_words + unf_ring_index(x, ring_words)], pixel, chunk, "its ring", j, x);
+                } else if (p > 0) {
+                  b = read_slot(above[unf_above_index(x)], pixel - CGAN_PNG_MAX_DIM, chunk, "the row above the pass", j, x);
+                }
+              }
+              l.above_left = b;
+            }
+            uint32_t v = 0;
+            if (active) {
+              const uint8_t* row = inflated + (size_t)y * (1 + rb);          // inside the inflated extent: y < H, x < W
+              uint32_t raw = 0;
+              for (uint32_t k = 0; k < bpp; ++k) raw |= (uint32_t)row[1 + (uint32_t)x * bpp + k] << (8 * k);
+              v = unfilter_pixel(l.filter, raw, l.cur, b, cc);
+              uint8_t* px = pixels + ((size_t)y * W + x) * bpp;             // inside the pixel extent
+              for (uint32_t k = 0; k < bpp; ++k) {
+                px[swap ? 1 - k : k] = (uint8_t)(v >> (8 * k));
+                l.ad.byte((raw >> (8 * k)) & 255u);
+              }
+              if (r == L - 1) {
+                const Slot s{v, (int64_t)p * CGAN_PNG_MAX_DIM + x, chunk};
+                if (j + 1 < waves) ring[(size_t)((j + 1) % waves) * ring_words + unf_ring_index(x, ring_words)] = s;
+                else above[unf_above_index(x)] = s;
+              }
+            }
+            l.prev = l.cur, l.cur = v;
+          }
+        }
+      }
+    }
+    for (int j = 0; j < waves; ++j)
+      for (int r = 0; r < L; ++r) {
+        const int y = unf_row(p, j, r, waves);
+        if (y < H) lanes[j * L + r].ad.end_piece(total - (uint32_t)(y + 1) * (1 + rb));
+      }
+  }
+  uint32_t s1 = 0, s2 = 0;
+  bool bad_filter = false;
+  for (int i = 0; i < waves * L; ++i) {
+    s1 = (s1 + lanes[i].ad.s1) % ADLER_MOD, s2 = (s2 + lanes[i].ad.s2) % ADLER_MOD;
+    bad_filter = bad_filter || lanes[i].bad;
+  }
+  delete[] shifted, delete[] lanes, delete[] ring, delete[] above;
+  if (rc) return rc;
+  *status = CGAN_PNG_OK;
+  why[0] = 0;
+  if (bad_filter || adler_value(s1, s2, total) != trailer) {
+    *status = CGAN_PNG_CORRUPT;
+    snprintf(why, why_len, "%s", bad_filter ? "a filter byte above 4" : "Adler-32 mismatch");
+  }
+  return 0;
+}
+
 // The twin: the kernels' two stages one after the other, every token and every pixel taken serially.
 //   inflated: inflated_bytes(desc) bytes, pixels: pixel_bytes(desc) bytes
 inline int host_decode(const uint8_t* stream, const cgan_png_desc* desc, uint8_t* inflated, uint8_t* pixels, int32_t* status, char* why,

@@ -15,9 +15,13 @@ reference's own and the host test compares.
 ``OmniLoader`` -- an iterable of collated batches, not a ``torch.utils.data.DataLoader``: its workers are THREADS that read
 and decode files into numpy arrays, one batch ahead of the consumer; the arrays of a task travel through one pinned
 buffer and one copy on a side stream, and the whole batch is then the one launch per task of ``compile_transforms``.
+With ``data.loaders.decode: device`` the threads only read and probe the PNG and JPEG files, and the batch's
+files are decoded by the device decoders (``png.py``, ``jpeg.py``) in one call per codec.
 
 Out of scope: the Logger's display helpers (``decode_segmap_merged_labels``, ...).
 """
+import collections
+import ctypes as C
 import json
 import os
 import time
@@ -27,7 +31,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import ops, parallel
+from . import _lib, jpeg, ops, parallel, png
 from .transforms import Compose, RawSource, compile_transforms, get_transforms, set_draws
 from .utils import env_to_path
 
@@ -190,6 +194,57 @@ def read_host(path, task, domain):
     return arr, known
 
 
+DECODE_MODES = ("host", "device")
+
+# A file a reader thread leaves to the device decoders (``decode="device"``): ``codec`` "png" or "jpeg", the
+# descriptor its ``probe`` filled, ``stream`` the bytes the decoder reads (a PNG file's zlib stream, a JPEG file as it is) and,
+# for a row-framed PNG candidate, its ``c_uint32`` table of row offsets; ``path``: the file, should the host have to read it
+FileRecord = collections.namedtuple("FileRecord", "codec desc stream table path")
+
+
+def raw_kind(task, domain):
+    """The ``ops.RAW_KINDS`` name ``raw_source`` wraps a decoded file of ``task`` in; None where the host converts the array
+    first (the real domain's depth) or the task has no raw form"""
+    if task in ("x", "m"):
+        return "x" if task == "x" else "mask"
+    if task == "s":
+        return "kitti_s" if domain == "kitti" else "palette_s"
+    if task == "d" and domain != "r":
+        return "unity_d" if domain == "s" else "kitti_d"
+    return None
+
+
+def device_takes(task, domain, channels, bit_depth):
+    """Whether the array a device decoder leaves of such a file -- [H, W] for one channel, [H, W, C] otherwise, uint8 or
+    uint16 -- is one the task's raw kind accepts (``ops.RAW_KINDS``): x: 8 bits, 3 or 4 channels; m: 8 bits; s: 8-bit RGBA
+    (kitti: RGB); d: 8 bits with 3 or 4 channels in the simulated domain, 16-bit grey in kitti."""
+    kind = raw_kind(task, domain)
+    if kind is None:
+        return False
+    _, _, dtype, dims, chans = ops.RAW_KINDS[kind]
+    nd = 2 if channels == 1 else 3
+    return dtype == {8: "uint8", 16: "uint16"}.get(bit_depth) and nd in dims and (chans is None or nd == 2 or channels in chans)
+
+
+def read_file(path, task, domain):
+    """``read_host`` for a loader that decodes on the device: a ``FileRecord`` for a PNG or JPEG file a device decoder takes
+    (``png.probe`` / ``jpeg.probe``, host only) and whose array the task accepts (``device_takes``); for every other file
+    exactly what ``read_host`` returns, so that whatever it raises comes from the same place."""
+    path = Path(path)
+    suffix = path.suffix.lower()
+    if suffix == ".png":
+        data = path.read_bytes()
+        d, _ = png.probe(data)
+        if d is not None and device_takes(task, domain, d.channels, d.bit_depth):
+            return FileRecord("png", d, png.stream_of(data, d), png.row_table(data, d) if d.rows else None, path)
+    elif suffix in (".jpg", ".jpeg") and task == "x":
+        data = path.read_bytes()
+        d, _ = jpeg.probe(data)
+        if d is not None and device_takes(task, domain, d.ncomp, 8):
+            return FileRecord("jpeg", d, data, None, path)
+    return read_host(path, task, domain)
+
+
 class OmniListDataset:
     """reference data.py:402-504: the samples of one ``opts.data.files[mode][domain]`` list (``.json`` or ``.yaml``; a
     name without ``/`` is looked up in ``opts.data.files.base``), cut to ``opts.data.max_samples``, each reduced to the
@@ -248,6 +303,10 @@ class OmniListDataset:
         """{task: (array, known)} of sample ``i``: the part of ``read_raw`` that runs in a reader thread"""
         return {task: read_host(env_to_path(path), task, self.domain) for task, path in self.samples_paths[i].items()}
 
+    def read_file(self, i):
+        """``read_host`` of a loader with ``decode="device"``: {task: FileRecord, or (array, known) as ``read_host`` gives}"""
+        return {task: read_file(env_to_path(path), task, self.domain) for task, path in self.samples_paths[i].items()}
+
     def wrap(self, task, array, known=None):
         """The ``RawSource`` of a device array of this dataset's ``task`` (a ``.pt`` map stays the tensor it is)"""
         if array.is_floating_point() and array.dim() == 4:
@@ -271,6 +330,7 @@ class _Slot:
     def __init__(self):
         self.pinned, self.dev = {}, {}
         self.uploaded = self.consumed = None
+        self.decoded = None             # decode="device": the decoder calls' outputs that the staged arrays are views of
 
     def buffers(self, task, nbytes, device):
         if task not in self.pinned or self.pinned[task].numel() < nbytes:
@@ -302,11 +362,21 @@ class OmniLoader:
     (``local_batch_size`` samples) out of ONE permutation that all ranks share.  ``rank=None, world=None``: the process
     group's when ``parallel.is_distributed()`` -- the generator's seed is then rank 0's draw, broadcast -- else 0 of 1.
     ``seed(n)`` must be called with the same ``n`` on every rank.  The transform draws stay per rank.  With
-    ``LOCAL_WORLD_SIZE`` in the environment the reader threads are at most ``16 // LOCAL_WORLD_SIZE`` (one at least)."""
+    ``LOCAL_WORLD_SIZE`` in the environment the reader threads are at most ``16 // LOCAL_WORLD_SIZE`` (one at least).
+
+    ``decode`` (``opts.data.loaders.decode``): "host" -- the above, the default -- or "device" (a cuda device
+    only): the reader threads run ``dataset.read_file``, which reads and probes a file and leaves every PNG or JPEG file the
+    device decoders take, and whose array the task accepts, as a ``FileRecord``; ``_decode`` puts all of a batch's such files
+    into one blob per codec and decodes them in one call (``ops.png_decode_rows`` / ``ops.png_decode``,
+    ``ops.jpeg_decode``), and the decoded arrays go to ``dataset.wrap`` with nothing known of them.  Every other file, and a
+    file the decoder reports as corrupt, goes through ``read_host`` as before.  The batches are the host mode's, bit for bit.
+    ``decode_counts``: files since construction by who decoded them; ``times["decode"]`` exists in device mode only."""
 
     def __init__(self, dataset, batch_size, num_workers=0, prefetch=1, shuffle=True, device=None, transform=None,
-                 rank=None, world=None):
-        self.dataset, self.batch_size = dataset, int(batch_size)
+                 rank=None, world=None, decode="host"):
+        if decode not in DECODE_MODES:
+            raise ValueError("OmniLoader: decode=%r; one of %s" % (decode, ", ".join(DECODE_MODES)))
+        self.dataset, self.batch_size, self.decode = dataset, int(batch_size), decode
         from_group = rank is None and world is None and parallel.is_distributed()
         if from_group:
             rank, world = parallel.rank(), parallel.world()
@@ -322,6 +392,8 @@ class OmniLoader:
         self.device = torch.device(device) if device is not None else _device(dataset.device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
+        if decode == "device" and self.device.type != "cuda":
+            raise ValueError("OmniLoader: decode=\"device\" needs a cuda device, got %s" % self.device)
         self.transform = transform if transform is not None else compile_transforms(dataset.opts, dataset.mode, dataset.domain)
         self.generator = torch.Generator()
         seed = int(torch.empty((), dtype=torch.int64).random_().item())
@@ -335,6 +407,9 @@ class OmniLoader:
         self.generator.manual_seed(seed)
         self.last_order = None
         self.times = {"read": 0.0, "stage": 0.0, "transform": 0.0, "batches": 0}     # host seconds, summed
+        if decode == "device":
+            self.times["decode"] = 0.0                  # the part of "stage" spent on the files the device decodes
+        self.decode_counts = {"png": 0, "jpeg": 0, "host": 0}      # files since construction, by who decoded them
         self._slots = [_Slot(), _Slot()]
         self._pool = self._coord = self._side = self._pending = None
 
@@ -353,10 +428,11 @@ class OmniLoader:
     # -------------------------------------------------------------------------------------------- the producer's half
     def _read(self, indices):
         t0 = time.perf_counter()
+        read = self.dataset.read_file if self.decode == "device" else self.dataset.read_host
         if self._pool is not None:
-            samples = list(self._pool.map(self.dataset.read_host, indices))
+            samples = list(self._pool.map(read, indices))
         else:
-            samples = [self.dataset.read_host(i) for i in indices]
+            samples = [read(i) for i in indices]
         self.times["read"] += time.perf_counter() - t0
         return samples
 
@@ -371,7 +447,8 @@ class OmniLoader:
             if slot.consumed is not None:
                 stream.wait_event(slot.consumed)        # the gather that last read the device buffers has run
             for task in samples[0]:
-                arrays = [s[task][0] for s in samples]
+                rows = [(k, s[task]) for k, s in enumerate(samples) if not isinstance(s[task], FileRecord)]
+                arrays = [v[0] for _, v in rows]
                 offsets, total = [], 0
                 for a in arrays:
                     offsets.append(total)
@@ -384,16 +461,87 @@ class OmniLoader:
                         host[off:off + a.nbytes] = a.reshape(-1).view(np.uint8)
                 if total:
                     dev[:total].copy_(pinned[:total], non_blocking=True)
-                for k, (a, off) in enumerate(zip(arrays, offsets)):
+                for (k, v), a, off in zip(rows, arrays, offsets):
                     if torch.is_tensor(a):
                         t = a.to(self.device)
                     else:
                         t = dev[off:off + a.nbytes].view(torch.from_numpy(a[:0]).dtype).view(a.shape)
-                    staged[k][task] = (t, samples[k][task][1])
+                    staged[k][task] = (t, v[1])
+            if self.decode == "device":
+                self.decode_counts["host"] += sum(not isinstance(v, FileRecord) for s in samples for v in s.values())
+                self._decode(samples, staged, slot)
+                staged = [{task: st[task] for task in s} for s, st in zip(samples, staged)]     # the tasks in the list's order
             slot.uploaded = torch.cuda.Event()
             slot.uploaded.record(stream)
         self.times["stage"] += time.perf_counter() - t0
         return staged
+
+    def _upload(self, slot, key, pieces, offsets, total):
+        """``pieces`` (buffers of bytes) at ``offsets`` of the slot's pinned buffer ``key``, one copy -> the device bytes"""
+        pinned, dev = slot.buffers(key, total, self.device)
+        host = pinned.numpy()
+        for piece, off in zip(pieces, offsets):
+            b = np.frombuffer(piece, dtype=np.uint8)
+            host[off:off + b.size] = b
+        dev[:total].copy_(pinned[:total], non_blocking=True)
+        return dev[:total]
+
+    def _decode(self, samples, staged, slot):
+        """The files the reader threads left to the device decoders (``FileRecord``), on the current stream: per codec the
+        bytes of ALL tasks' files in one blob in the slot's pinned buffer, one upload each of the blob, of the descriptors and
+        (PNG) of the row tables, ONE decoder call and one wait for its status words.  The decoded arrays -- views into the
+        call's output, [H, W] for one channel, [H, W, C] otherwise -- go to ``staged`` with nothing known of them:
+        ``RawSource`` finds min / max and the mask's threshold on the device.  A file whose status is not OK is read again by
+        ``read_host`` and uploaded on its own.
+
+        The output is allocated under this stream and read by the consumer's: the SLOT holds it (``slot.decoded``) until
+        the next ``_stage`` of the slot, which drops it only behind this stream's wait for the slot's ``consumed`` event --
+        the same rule that protects ``slot.dev``; no ``record_stream``."""
+        t0 = time.perf_counter()
+        held = []
+        for codec in ("png", "jpeg"):
+            todo = [(k, task, v) for k, s in enumerate(samples) for task, v in s.items()
+                    if isinstance(v, FileRecord) and v.codec == codec]
+            if not todo:
+                continue
+            descs = ((_lib.PngDesc if codec == "png" else _lib.JpegDesc) * len(todo))()
+            offsets, at, out_at = [], 0, 0
+            for i, (_, _, v) in enumerate(todo):
+                d = v.desc
+                d.blob_offset, d.out_offset = at, out_at
+                offsets.append(at)
+                at += -(-len(v.stream) // 16) * 16
+                pixels = d.width * d.height * (d.channels * (d.bit_depth // 8) if codec == "png" else d.ncomp)
+                out_at += -(-pixels // 16) * 16
+                descs[i] = d
+            blob = self._upload(slot, codec, [v.stream for _, _, v in todo], offsets, at)
+            descs_dev = self._upload(slot, codec + "_descs", [descs], [0], C.sizeof(descs))
+            if codec == "jpeg":
+                out, status = ops.jpeg_decode(blob, descs, descs_dev)
+            elif any(v.table is not None for _, _, v in todo):
+                tables = (C.c_uint32 * sum(len(v.table) for _, _, v in todo if v.table is not None))()
+                words = 0
+                for _, _, v in todo:
+                    if v.table is not None:
+                        C.memmove(C.byref(tables, 4 * words), v.table, 4 * len(v.table))
+                        words += len(v.table)
+                tables_dev = self._upload(slot, "png_tables", [tables], [0], 4 * words).view(torch.int32)
+                out, status, _ = ops.png_decode_rows(blob, descs, descs_dev, tables, tables_dev)
+            else:
+                out, status = ops.png_decode(blob, descs, descs_dev)
+            held.append(out)
+            view = png.image_view if codec == "png" else jpeg.image_view
+            for (k, task, v), d, s in zip(todo, descs, status.tolist()):            # the one wait of this codec's call
+                if s == 0:
+                    img = view(out, d)
+                    staged[k][task] = (img.view(d.height, d.width) if img.shape[2] == 1 else img, {})
+                    self.decode_counts[codec] += 1
+                else:
+                    arr, known = read_host(v.path, task, self.dataset.domain)
+                    staged[k][task] = ((arr if torch.is_tensor(arr) else torch.from_numpy(arr)).to(self.device), known)
+                    self.decode_counts["host"] += 1
+        slot.decoded = held
+        self.times["decode"] += time.perf_counter() - t0
 
     def _prepare(self, indices, slot):
         """(reader threads ->) pinned buffers -> device, on the side stream; runs in the coordinator thread"""
@@ -491,13 +639,17 @@ def get_loader(mode, domain, opts, prefetch=1, device=None, *, rank=None, world=
     dropped, ``min(opts.data.loaders.num_workers, 16)`` reader threads.  Either batch size is the global one of a
     data-parallel run; ``rank`` / ``world`` as ``OmniLoader`` reads them."""
     loaders = opts.data.get("loaders") or {}
+    decode = loaders.get("decode", "host")
+    if decode not in DECODE_MODES:
+        raise ValueError("get_loader: data.loaders.decode = %r; one of %s" % (decode, ", ".join(DECODE_MODES)))
     kitti = opts.train.get("kitti") or {}
     if domain != "kitti" or not kitti.get("pretrain") or not kitti.get("batch_size"):
         batch_size = loaders.get("batch_size", 4)
     else:
         batch_size = kitti.get("batch_size", 4)
     return OmniLoader(OmniListDataset(mode, domain, opts, device=device), batch_size,
-                      num_workers=loaders.get("num_workers", 8), prefetch=prefetch, device=device, rank=rank, world=world)
+                      num_workers=loaders.get("num_workers", 8), prefetch=prefetch, device=device, rank=rank, world=world,
+                      decode=decode)
 
 
 def loader_domains(opts):

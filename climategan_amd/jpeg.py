@@ -55,6 +55,11 @@ def upload(descs_and_data, device):
             torch.frombuffer(bytearray(descs), dtype=torch.uint8).to(device))
 
 
+def image_view(out, d):
+    """File ``d``'s uint8 [H, W, C] pixels in the output of ``ops.jpeg_decode``"""
+    return out[d.out_offset:d.out_offset + d.width * d.height * d.ncomp].view(d.height, d.width, d.ncomp)
+
+
 def try_decode(files, device="cuda", subseq_bytes=0):
     """``decode`` without raising for a file's sake -> (images, reasons): ``images[i]`` is None for a file that was not
     decoded and ``reasons[i]`` says why."""
@@ -76,7 +81,7 @@ def try_decode(files, device="cuda", subseq_bytes=0):
             if s != ops.JPEG_OK:
                 reasons[i] = STATUS_TEXT[ops.JPEG_NOT_CONVERGED if s & ops.JPEG_NOT_CONVERGED else ops.JPEG_CORRUPT]
             else:
-                images[i] = out[d.out_offset:d.out_offset + d.width * d.height * d.ncomp].view(d.height, d.width, d.ncomp)
+                images[i] = image_view(out, d)
     return images, reasons
 
 

@@ -71,6 +71,24 @@ def upload(descs_and_data, device):
             torch.frombuffer(bytearray(descs), dtype=torch.uint8).to(device))
 
 
+def row_table(data, d):
+    """The row offsets of one probed candidate (``d.rows != 0``) -> a ``c_uint32`` array of rows + 1 words: what a caller
+    that assembles its own batch (the loaders) puts one file behind the other.  Host only."""
+    data = bytes(data)
+    table = (C.c_uint32 * (d.rows + 1))()
+    _lib.check(_lib.load().cgan_png_row_table_host(data, len(data), C.addressof(d), table), "cgan_png_row_table_host")
+    return table
+
+
+def image_view(out, d):
+    """File ``d``'s pixels in the output of ``ops.png_decode`` / ``ops.png_decode_rows``: uint8 [H, W, C], ``torch.uint16``
+    [H, W, 1] for 16-bit grey"""
+    px = out[d.out_offset:d.out_offset + _pixel_bytes(d)]
+    if d.bit_depth == 16:
+        px = px.view(torch.uint16)
+    return px.view(d.height, d.width, d.channels)
+
+
 def row_tables(descs, datas, device):
     """The row offsets of a batch's candidates (``descs[k].rows != 0``; ``datas[k]``: that file's bytes) as
     ``ops.png_decode_rows`` takes them -> (tables, tables_dev): one ``c_uint32`` array, every candidate's rows + 1 words one
@@ -111,10 +129,7 @@ def try_decode(files, device="cuda"):
             if s != ops.PNG_OK:
                 reasons[i] = STATUS_TEXT[ops.PNG_CORRUPT]
             else:
-                px = out[d.out_offset:d.out_offset + _pixel_bytes(d)]
-                if d.bit_depth == 16:
-                    px = px.view(torch.uint16)
-                images[i] = px.view(d.height, d.width, d.channels)
+                images[i] = image_view(out, d)
     return images, reasons
 
 

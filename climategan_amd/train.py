@@ -53,6 +53,8 @@ def train_defaults():
     """The part of shared/trainer/defaults.yaml that the loaders and the loop read (line numbers of that file), over
     ``default_opts()``.  The file lists have no default: the reference's are paths of its authors' cluster."""
     opts = default_opts()
+    # data.loaders.decode ("host" | "device", DESIGN 4.23) is read by get_loader and is deliberately not listed: an absent key
+    # means "host", and the loaders' dictionary stays the reference's two entries
     _merge_into(opts, {
         "data": {"max_samples": -1, "check_samples": False, "loaders": {"batch_size": 6, "num_workers": 6},   # :25, 38-41
                  "normalization": "default",                                                                  # :42

@@ -38,7 +38,8 @@ typedef enum {
   CGAN_ERR_BAD_ARG = -1,      /* null pointer, bad shape, unsupported option */
   CGAN_ERR_UNSUPPORTED = -2,  /* valid request this build has no kernel for */
   CGAN_ERR_WORKSPACE = -3,    /* workspace too small */
-  CGAN_ERR_HIP = -4           /* HIP runtime error (launch failure ...) */
+  CGAN_ERR_HIP = -4,          /* HIP runtime error (launch failure ...) */
+  CGAN_ERR_INTERNAL = -5      /* the library broke a rule of its own (a host twin's schedule check) */
 } cgan_status_t;
 
 typedef enum { CGAN_F16 = 0, CGAN_BF16 = 1, CGAN_F32 = 2 /* cgan_allreduce_bucket only */ } cgan_dtype_t;
@@ -808,6 +809,16 @@ size_t cgan_png_decode_rows_workspace_bytes(const cgan_png_desc* descs_host, con
 int cgan_png_decode_rows(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host, const cgan_png_desc* descs_dev,
                          const uint32_t* tables_host, const uint32_t* tables_dev, size_t table_len, int32_t n, uint8_t* out,
                          size_t out_bytes, int32_t* status, int32_t* path, void* workspace, size_t workspace_bytes, void* stream);
+/* The unfilter stage of both device calls: one workgroup of *waves waves per file, wave j running
+ * j * (64 + *lag) steps behind wave 0, one barrier per *prefetch steps.  cgan_png_unfilter_wide_params: the compiled values.
+ * cgan_png_unfilter_wide_host (host only): that schedule for any 1 <= waves <= 16 and any lag that is a multiple of the
+ * prefetch, step by step, on the inflated bytes of one file (height * (1 + row bytes), as cgan_png_decode_host leaves them)
+ * and the stream's Adler-32 trailer -> pixels and *status as cgan_png_decode_host gives them.  Every value that crosses a wave
+ * or a pass is checked against the barriers: read before it was written, after it was overwritten, or in the chunk that wrote
+ * it: CGAN_ERR_INTERNAL, the reason in cgan_last_error. */
+void cgan_png_unfilter_wide_params(int32_t* waves, int32_t* lag, int32_t* prefetch);
+int cgan_png_unfilter_wide_host(const cgan_png_desc* desc, const uint8_t* inflated, uint32_t trailer, int32_t waves, int32_t lag,
+                                uint8_t* pixels, int32_t* status);
 
 /* Smog event (Trainer.compute_smog, climategan/trainer.py:1879-1939, parameters shared/trainer/events.yaml:9-14):
  * irradiance = srgb2lrgb(normalize(x)) (tutils.py:534-538), depth = normalize(1 / normalize(d, 0.3, 1), 0.1, 1)
