@@ -294,6 +294,10 @@ _SIGNATURES = {
     "cgan_png_decode_host": (C.c_int, [_P, _P, _P, _P, _P]),
     "cgan_png_decode_workspace_bytes": (C.c_size_t, [_P, C.c_int32]),
     "cgan_png_decode": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "cgan_png_inflate_lanes_params": (None, [_P, _P]),
+    "cgan_png_decode_lanes": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P, C.c_size_t, _P, C.c_int32,
+                                        C.c_int32]),
+    "cgan_png_inflate_lanes_host": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "cgan_png_row_table_host": (C.c_int, [_P, C.c_size_t, _P, _P]),
     "cgan_png_decode_rows_host": (C.c_int, [_P] * 7),
     "cgan_png_decode_rows_workspace_bytes": (C.c_size_t, [_P, _P, C.c_size_t, C.c_int32]),

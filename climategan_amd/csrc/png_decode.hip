@@ -11,7 +11,12 @@
 //                    distance is shorter than its length as a modular repeat).  The last 32 KiB of output are kept in an LDS
 //                    ring, which is all a match ever reads; the workspace is only written.  Nothing is written to the ring
 //                    ahead of its turn: a byte written early would take the slot of the byte 32 KiB before it, which a match
-//                    still to come may read.  Leaves the stream's Adler-32 trailer.
+//                    still to come may read.  Leaves the stream's Adler-32 trailer.  Since DESIGN 4.24 the serial form:
+//                    cgan_png_decode_lanes with subseq_bits = 0.
+//   inflate_lanes_kernel  the same workgroup with the decode spread over the 64 lanes: inside a block of codes
+//                    every lane decodes the tokens that begin in its subsequence of a window, first from its own first bit,
+//                    again from its predecessor's exit bit until no entry changes; the committed lanes' tokens go through
+//                    the same execute step 64 at a time.  What cgan_png_decode and cgan_png_decode_rows' fallback launch.
 //   unfilter_kernel  one workgroup of UNFILTER_WAVES waves per file, 64 rows per wave at a time as one skewed
 //                    wavefront across the waves: lane r of a wave is at pixel t - r in the wave's step t, its left neighbour
 //                    is its own last result, the two pixels above come from lane r - 1 by __shfl_up; lane 0 reads the row
@@ -26,7 +31,8 @@
 //                        shape as inflate_kernel -- lane 0 decodes up to 64 tokens (decode_tokens in MODE_ROW: the reader
 //                        bounded to the row's chunk), the wave executes them -- with the row itself as the window, in dynamic
 //                        LDS sized from the batch's longest row.  Whatever a row does not satisfy ORs the file's "refused" word.
-//   inflate_kernel<true> the serial kernel for the files that are no candidates or were refused; the others' workgroups return.
+//   inflate_lanes_kernel<true>  the whole-stream kernel for the files that are no candidates or were refused; the others'
+//                        workgroups return.
 // Launches and memsets per call: 1 memset (status) + layout + row inflate + serial inflate + unfilter = 5.  The bounds above
 // hold: a row's reader ends with its chunk, a token's bytes end inside the row, a match starts at or behind the row's first
 // byte, the row buffer's indices are reduced modulo its size, the table's offsets are checked on the host and again by the wave.
@@ -282,6 +288,173 @@ __global__ __launch_bounds__(T) void inflate_kernel(const uint8_t* __restrict__ 
   }
 }
 
+// ---- the inflate across the wave's lanes ----------------------------------------------------------------------
+// inflate_kernel's execute step on up to 64 tokens held one per lane (`have`: this lane holds one): the commit's checks first,
+// wave-uniformly -- the tokens from the first refused one on are dropped and *refused is set -- then the prefix sum, the runs of
+// literals at once, every match or stored run by all lanes, in the stream's order.  All lanes call it; -> the new `pos`.
+__device__ inline uint32_t execute_tokens(Token k, bool have, uint32_t pos, uint32_t limit, uint8_t* ring, uint8_t* __restrict__ out,
+                                          const uint8_t* __restrict__ stream, bool* refused) {
+  const uint32_t lane = threadIdx.x;
+  if (!have) k = Token{0, 0, 0, 0};
+  uint32_t incl = k.len;
+  for (int off = 1; off < T; off <<= 1) {
+    const uint32_t v = __shfl_up(incl, off);
+    if ((int)lane >= off) incl += v;
+  }
+  const uint32_t mine = pos + incl - k.len;             // at most 64 * 65535 behind pos <= 2^29: no overflow
+  const unsigned long long no = __ballot(have && (mine > limit || token_refused(k, mine, limit)));
+  *refused = no != 0;
+  if (no) have = have && (int)lane < __ffsll(no) - 1;   // the tokens in front of the first refused one are inside the extent
+  if (!have) k = Token{0, 0, 0, 0};
+  const uint32_t w0 = (uint32_t)k.len | ((uint32_t)k.kind << 16);
+  unsigned long long todo = __ballot(have && k.kind != TOK_LITERAL);
+  int done = -1;
+  while (todo) {                                        // at most 64 turns, the same in every lane
+    const int i = __ffsll(todo) - 1;
+    todo &= todo - 1;
+    if (have && (int)lane > done && (int)lane < i) {
+      ring[mine & (WINDOW - 1)] = k.lit;
+      out[mine] = k.lit;
+    }
+    __syncthreads();
+    const uint32_t m0 = __shfl(w0, i), arg = __shfl(k.arg, i), q = __shfl(mine, i);
+    const uint32_t len = m0 & 0xFFFFu;
+    if ((m0 >> 16) == TOK_MATCH) {
+      const uint32_t from = q - arg;                    // arg <= q: token_refused
+      for (uint32_t j = lane; j < len; j += T) {
+        const uint8_t v = ring[(from + (arg < len ? j % arg : j)) & (WINDOW - 1)];
+        ring[(q + j) & (WINDOW - 1)] = v;
+        out[q + j] = v;
+      }
+    } else {
+      for (uint32_t j = lane; j < len; j += T) {        // arg + len <= stream_bytes: block_header checked it
+        const uint8_t v = stream[arg + j];
+        ring[(q + j) & (WINDOW - 1)] = v;
+        out[q + j] = v;
+      }
+    }
+    __syncthreads();
+    done = i;
+  }
+  if (have && (int)lane > done) {                       // the literals behind the last match
+    ring[mine & (WINDOW - 1)] = k.lit;
+    out[mine] = k.lit;
+  }
+  const unsigned long long kept = __ballot(have);       // a prefix of the lanes
+  const uint32_t total = kept ? __shfl(incl, 63 - __clzll(kept)) : 0u;
+  __syncthreads();
+  return pos + total;
+}
+
+// One workgroup of one wave per file, as inflate_kernel.  Lane 0 owns the stream's state (Inflate) and reads block headers,
+// stored blocks and the trailer serially (phase_step); inside a block of codes the wave decodes windows of 64 * S bits by the
+// window rule of png_decode_core.h -- every lane its subsequence into its own LDS slots, again from its predecessor's exit bit
+// until no entry changes -- and commits the lanes up to the first that did not run to its range's end: their tokens pass
+// through execute_tokens 64 at a time, in the stream's order.  A token of a lane that is not committed is never read.
+// Every barrier stands under conditions all lanes share (ctl[], ballots, shuffled values); none inside the per-lane decode.
+// Loops: the passes are counted to 64, a lane's tokens to `cap`, a window's commit to 64 * cap tokens, and every window or
+// serial step consumes a bit of the stream or ends the file.  Slots, tables and ring are indexed through slot_index, masks
+// and the sizes of their arrays; the readers never leave the stream.
+template <bool PREDICATED>
+__global__ __launch_bounds__(T) void inflate_lanes_kernel(const uint8_t* __restrict__ blob, const cgan_png_desc* __restrict__ descs,
+                                                          Workspace w, int32_t* __restrict__ status, int32_t* __restrict__ path,
+                                                          uint32_t S, uint32_t cap) {
+  __shared__ Tables tables;
+  __shared__ Token slot[LANES * LANE_SLOTS];
+  __shared__ Token tok[BATCH];
+  __shared__ uint32_t ctl[3];                 // stored tokens of the serial step; what follows; the bit the window starts at
+  __shared__ uint16_t base[LANES + 1];        // the committed lanes' tokens: lane i's are base[i] .. base[i + 1]
+  __shared__ uint8_t ring[WINDOW];
+  const int file = blockIdx.x;
+  const uint32_t lane = threadIdx.x;
+  const cgan_png_desc d = descs[file];
+  if constexpr (PREDICATED) {
+    const bool by_rows = d.rows != 0 && w.refused[file] == 0;       // the same in every lane
+    if (lane == 0) path[file] = by_rows ? 1 : (d.rows != 0 ? 2 : 0);
+    if (by_rows) return;
+  }
+  const uint8_t* stream = blob + d.blob_offset;
+  uint8_t* out = w.inflated + w.layout[file];
+  const uint32_t limit = inflated_bytes(d);
+  if (cap > LANE_SLOTS) cap = LANE_SLOTS;
+  Inflate s;
+  s.start(stream, d.stream_bytes, limit);               // every lane the same; lane 0's is the one that advances
+  uint32_t pos = 0;                                     // bytes executed so far, the same in every lane
+  bool corrupt = false;                                 // found at a commit, the same in every lane
+  constexpr uint32_t ENDED = 0, SERIAL = 1, CODES = 2;
+  for (;;) {
+    // the serial phases, lane 0: up to BATCH steps, each of which consumes stream or ends the file
+    if (lane == 0) {
+      uint32_t nt = 0, steps = 0;
+      s.out = pos;
+      while (s.phase != PHASE_CODES && s.phase != PHASE_DONE && !s.err && steps++ < BATCH) nt = phase_step(s, tables, tok, nt);
+      ctl[0] = nt;
+      ctl[1] = (s.phase == PHASE_DONE || s.err) ? ENDED : (s.phase == PHASE_CODES ? CODES : SERIAL);
+      ctl[2] = (uint32_t)s.r.used();
+    }
+    __syncthreads();
+    const uint32_t nt = ctl[0] < BATCH ? ctl[0] : BATCH, next = ctl[1];
+    uint32_t P = ctl[2];
+    bool refused;
+    pos = execute_tokens(tok[lane], lane < nt, pos, limit, ring, out, stream, &refused);      // stored runs: checked by phase_step
+    corrupt = refused;
+    if (next == ENDED || corrupt) break;
+    if (next == SERIAL) continue;
+    // windows, until one commits an end-of-block symbol, an invalid symbol or a refused token
+    uint32_t flag = SUB_NONE;
+    while (flag != SUB_EOB) {
+      uint32_t entry = lane_first_entry(P, lane, S);
+      const uint32_t end = lane_end(P, lane, S);
+      SubExit ex{entry, SUB_NONE, 0};
+      bool changed = true;
+      for (uint32_t pass = 0; pass < LANES; ++pass) {
+        if (changed) ex = entry >= end ? SubExit{entry, SUB_NONE, 0} : decode_subseq(stream, d.stream_bytes, entry, tables, end, slot, lane, cap);
+        const uint32_t before = __shfl_up(ex.bit, 1), before_flag = __shfl_up(ex.flag, 1);
+        changed = lane > 0 && before_flag == SUB_NONE && before != entry;
+        if (changed) entry = before;
+        if (!__any(changed)) break;
+      }
+      const unsigned long long stopped = __ballot(ex.flag != SUB_NONE);
+      const int c = stopped ? __ffsll(stopped) - 1 : (int)LANES - 1;
+      flag = __shfl(ex.flag, c);
+      P = __shfl(ex.bit, c);
+      const uint32_t count = (int)lane <= c ? (ex.count < cap ? ex.count : cap) : 0u;
+      uint32_t incl = count;
+      for (int off = 1; off < T; off <<= 1) {
+        const uint32_t v = __shfl_up(incl, off);
+        if ((int)lane >= off) incl += v;
+      }
+      if (lane == 0) base[0] = 0;
+      base[lane + 1] = (uint16_t)incl;                  // at most 64 * LANE_SLOTS
+      const uint32_t total = __shfl(incl, T - 1);
+      __syncthreads();                                  // the slots and base[] are written
+      for (uint32_t g0 = 0; g0 < total && !corrupt; g0 += BATCH) {
+        const uint32_t g = g0 + lane;
+        const bool have = g < total;
+        uint32_t l = 0;                                 // the lane whose tokens hold token g: base[l] <= g < base[l + 1]
+        for (uint32_t step = LANES / 2; step; step >>= 1)
+          if (base[l + step] <= g) l += step;
+        Token k{0, 0, 0, 0};
+        if (have) k = slot[slot_index(l, g - base[l])];
+        pos = execute_tokens(k, have, pos, limit, ring, out, stream, &refused);
+        corrupt = refused;
+      }
+      __syncthreads();                                  // the slots are read before the next window writes them
+      if (flag == SUB_BAD) corrupt = true;
+      if (corrupt) break;
+    }
+    if (corrupt) break;
+    if (lane == 0) {                                    // behind the end-of-block symbol: the next header, or the trailer
+      s.r.seat_bit(P);
+      s.phase = s.last ? PHASE_TRAILER : PHASE_HEADER;
+    }
+  }
+  if (lane == 0) {
+    if (corrupt || s.err || s.phase != PHASE_DONE) atomicOr(&status[file], (int32_t)CGAN_PNG_CORRUPT);
+    w.adler[file] = s.adler;
+  }
+}
+
 // One workgroup of NW waves per file (the schedule is png_decode_core.h's unf_* functions, which the host twin
 // host_unfilter_wide runs step by step).  Inside a wave: a skewed wavefront, lane r at pixel t - r in the wave's step t, the left
 // neighbour its own last result, the two pixels above from lane r - 1 by __shfl_up.  Between waves: wave j runs j * (64 + LAG)
@@ -454,10 +627,25 @@ extern "C" size_t cgan_png_decode_workspace_bytes(const cgan_png_desc* descs_hos
   return carve(nullptr, descs_host, n).bytes;
 }
 
-extern "C" int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
-                               const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status,
-                               void* workspace, size_t workspace_bytes, void* stream) {
-  const char* what = "cgan_png_decode";
+namespace {
+
+// the whole-stream inflate in its two forms: subseq_bits = 0 the serial kernel, else the lanes' windows
+template <bool PREDICATED>
+void launch_inflate(int32_t n, hipStream_t s, const uint8_t* blob, const cgan_png_desc* descs_dev, const Workspace& w, int32_t* status,
+                    int32_t* path, int32_t subseq_bits, int32_t lane_tokens) {
+  if (subseq_bits == 0)
+    hipLaunchKernelGGL(inflate_kernel<PREDICATED>, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status, path);
+  else
+    hipLaunchKernelGGL(inflate_lanes_kernel<PREDICATED>, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status, path, (uint32_t)subseq_bits,
+                       (uint32_t)lane_tokens);
+}
+
+int png_decode_impl(const char* what, const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
+                    const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace,
+                    size_t workspace_bytes, void* stream, int32_t subseq_bits, int32_t lane_tokens) {
+  CGAN_REQUIRE(lanes_params_ok(subseq_bits, lane_tokens),
+               "%s: subseq_bits = %d, lane_tokens = %d: 0 or a multiple of 32 up to %u, and 1 .. %u, expected", what, subseq_bits,
+               lane_tokens, SUBSEQ_BITS_MAX, LANE_SLOTS);
   CGAN_REQUIRE(blob && descs_dev && out && status && workspace, "%s: null pointer", what);
   if (const int rc = descs_ok(what, descs_host, n, blob_bytes, true, out_bytes)) return rc;
   CGAN_REQUIRE(reinterpret_cast<uintptr_t>(blob) % 4 == 0, "%s: the blob is not 4-byte aligned", what);
@@ -474,11 +662,40 @@ extern "C" int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cga
   }
   hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(64), 0, s, descs_dev, n, w.layout);
   CGAN_CHECK_LAUNCH("cgan_png_decode (layout)");
-  hipLaunchKernelGGL(inflate_kernel<false>, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status, static_cast<int32_t*>(nullptr));
+  launch_inflate<false>(n, s, blob, descs_dev, w, status, nullptr, subseq_bits, lane_tokens);
   CGAN_CHECK_LAUNCH("cgan_png_decode (inflate)");
   launch_unfilter(n, s, descs_dev, w, out, status);
   CGAN_CHECK_LAUNCH("cgan_png_decode (unfilter)");
   return CGAN_OK;
+}
+
+}  // namespace
+
+extern "C" int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
+                               const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  return png_decode_impl("cgan_png_decode", blob, blob_bytes, descs_host, descs_dev, n, out, out_bytes, status, workspace,
+                         workspace_bytes, stream, (int32_t)SUBSEQ_BITS_DEFAULT, (int32_t)LANE_TOKENS_DEFAULT);
+}
+
+extern "C" int cgan_png_decode_lanes(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
+                                     const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                                     void* workspace, size_t workspace_bytes, void* stream, int32_t subseq_bits, int32_t lane_tokens) {
+  return png_decode_impl("cgan_png_decode_lanes", blob, blob_bytes, descs_host, descs_dev, n, out, out_bytes, status, workspace,
+                         workspace_bytes, stream, subseq_bits, lane_tokens);
+}
+
+extern "C" void cgan_png_inflate_lanes_params(int32_t* subseq_bits, int32_t* lane_tokens) {
+  if (subseq_bits) *subseq_bits = (int32_t)SUBSEQ_BITS_DEFAULT;
+  if (lane_tokens) *lane_tokens = (int32_t)LANE_TOKENS_DEFAULT;
+}
+
+extern "C" int cgan_png_inflate_lanes_host(const uint8_t* stream, const cgan_png_desc* desc, int32_t subseq_bits, int32_t lane_tokens,
+                                           uint8_t* inflated, uint32_t* trailer, uint32_t* stats, int32_t* status) {
+  char why[200] = "";
+  const int rc = host_inflate_lanes(stream, desc, subseq_bits, lane_tokens, inflated, trailer, stats, status, why, sizeof(why));
+  if (rc || *status) cgan_set_error("cgan_png_inflate_lanes_host: %s", why);
+  return rc ? CGAN_ERR_BAD_ARG : CGAN_OK;
 }
 
 // ---- row-framed files ------------------------------------------------------------------------------------
@@ -560,7 +777,7 @@ extern "C" int cgan_png_decode_rows(const uint8_t* blob, size_t blob_bytes, cons
                        cap);
     CGAN_CHECK_LAUNCH("cgan_png_decode_rows (rows)");
   }
-  hipLaunchKernelGGL(inflate_kernel<true>, dim3(n), dim3(T), 0, s, blob, descs_dev, w, status, path);
+  launch_inflate<true>(n, s, blob, descs_dev, w, status, path, (int32_t)SUBSEQ_BITS_DEFAULT, (int32_t)LANE_TOKENS_DEFAULT);
   CGAN_CHECK_LAUNCH("cgan_png_decode_rows (inflate)");
   launch_unfilter(n, s, descs_dev, w, out, status);
   CGAN_CHECK_LAUNCH("cgan_png_decode_rows (unfilter)");

@@ -6,6 +6,8 @@
 //   Reader           the bit reader: a 64-bit window refilled a word at a time, never a byte outside the stream
 //   Tables           the code tables of the block being decoded: a direct table for short codes, canonical counts behind it
 //   decode_tokens    the inflate step: the stream from where it stands -> a batch of tokens (literal, match, stored run)
+//   decode_subseq    the same step for one lane of a wave: the tokens that begin in a range of bits, and the
+//                    window rule's few shared functions
 //   Inflate::start_row   the same step on one row's chunk of a row-framed file: the reader bounded to the chunk
 //   unfilter_pixel   the five predictors on up to four bytes at once, selected by the row's filter byte
 //   Adler            the checksum as sums that can be split over rows and added up
@@ -65,6 +67,11 @@ struct Reader {
     next = at & ~3u, n = 0, win = 0;
     refill();
     take(8 * (at & 3u));
+  }
+  // re-seat at bit `at` of the stream (at <= 2^31 + 2^16; behind the stream's end zeros enter, as in a refill)
+  PNG_HD void seat_bit(uint32_t at) {
+    seat(at >> 3);
+    take(at & 7u);                                         // seat leaves at least 8 bits
   }
   PNG_HD uint32_t word() const {
     uint32_t w = 0;
@@ -304,6 +311,46 @@ PNG_HD inline bool block_header(Inflate& s, Tables& t) {
   return true;
 }
 
+// One step of a phase other than PHASE_CODES: a block's header, a stored block's run (a token, unless it is empty), the
+// trailer.  Appends to tok[nt] where it has a token and returns the new count.
+PNG_HD inline uint32_t phase_step(Inflate& s, Tables& t, Token* tok, uint32_t nt) {
+  Reader& r = s.r;
+  if (s.phase == PHASE_HEADER) {
+    if (!block_header(s, t) || r.past_end()) s.err = CGAN_PNG_CORRUPT;
+    if (s.mode == MODE_ROW && s.last) s.err = CGAN_PNG_CORRUPT;      // a final block inside a row's chunk
+    return nt;
+  }
+  if (s.phase == PHASE_STORED) {
+    if (s.stored_left) {
+      if (s.stored_left > s.limit - s.out) {
+        s.err = CGAN_PNG_CORRUPT;
+        return nt;
+      }
+      tok[nt++] = Token{(uint16_t)s.stored_left, (uint8_t)TOK_STORED, 0, s.stored_at};
+      s.out += s.stored_left;
+    }
+    // restart the reader behind the run: at the word that holds the byte, the bits before the byte dropped
+    const uint32_t at = s.stored_at + s.stored_left;
+    r.seat(at);
+    s.stored_left = 0;
+    s.phase = s.last ? PHASE_TRAILER : PHASE_HEADER;
+    if (s.mode == MODE_ROW && at == r.len) {                         // the row-end rule: the chunk ends with this stored block
+      if (s.out != s.limit) s.err = CGAN_PNG_CORRUPT;
+      s.phase = PHASE_DONE;
+    }
+    return nt;
+  }
+  // PHASE_TRAILER
+  r.take(r.n & 7u);
+  r.refill();
+  uint32_t a = 0;
+  for (int k = 0; k < 4; ++k) a = (a << 8) | r.bits(8);
+  if (r.past_end() || s.out != s.limit) s.err = CGAN_PNG_CORRUPT;
+  s.adler = a;
+  s.phase = PHASE_DONE;
+  return nt;
+}
+
 // Decodes until `max_tok` tokens stand in tok[], the stream is done (PHASE_DONE) or an error is found (s.err).  Every turn of
 // the loop consumes at least one bit of the stream or leaves the loop, and a reader that has run past the stream's end is an
 // error, so the turns are bounded by 8 * stream bytes whatever the bytes are.
@@ -311,39 +358,8 @@ PNG_HD inline uint32_t decode_tokens(Inflate& s, Tables& t, Token* tok, uint32_t
   uint32_t nt = 0;
   Reader& r = s.r;
   while (nt < max_tok && s.phase != PHASE_DONE && !s.err) {
-    if (s.phase == PHASE_HEADER) {
-      if (!block_header(s, t) || r.past_end()) s.err = CGAN_PNG_CORRUPT;
-      if (s.mode == MODE_ROW && s.last) s.err = CGAN_PNG_CORRUPT;      // a final block inside a row's chunk
-      continue;
-    }
-    if (s.phase == PHASE_STORED) {
-      if (s.stored_left) {
-        if (s.stored_left > s.limit - s.out) {
-          s.err = CGAN_PNG_CORRUPT;
-          continue;
-        }
-        tok[nt++] = Token{(uint16_t)s.stored_left, (uint8_t)TOK_STORED, 0, s.stored_at};
-        s.out += s.stored_left;
-      }
-      // restart the reader behind the run: at the word that holds the byte, the bits before the byte dropped
-      const uint32_t at = s.stored_at + s.stored_left;
-      r.seat(at);
-      s.stored_left = 0;
-      s.phase = s.last ? PHASE_TRAILER : PHASE_HEADER;
-      if (s.mode == MODE_ROW && at == r.len) {                         // the row-end rule: the chunk ends with this stored block
-        if (s.out != s.limit) s.err = CGAN_PNG_CORRUPT;
-        s.phase = PHASE_DONE;
-      }
-      continue;
-    }
-    if (s.phase == PHASE_TRAILER) {
-      r.take(r.n & 7u);
-      r.refill();
-      uint32_t a = 0;
-      for (int k = 0; k < 4; ++k) a = (a << 8) | r.bits(8);
-      if (r.past_end() || s.out != s.limit) s.err = CGAN_PNG_CORRUPT;
-      s.adler = a;
-      s.phase = PHASE_DONE;
+    if (s.phase != PHASE_CODES) {
+      nt = phase_step(s, t, tok, nt);
       continue;
     }
     r.refill();
@@ -383,6 +399,80 @@ PNG_HD inline uint32_t decode_tokens(Inflate& s, Tables& t, Token* tok, uint32_t
   }
   return nt;
 }
+
+// ---- the inflate step across a wave's lanes ---------------------------------------------------------------------
+// Inside a block of Huffman codes the state of a decode is one number, the bit at which the next token begins, and a decode
+// that starts at a wrong bit falls into step with the right one after a few tokens.  A window of LANES * S bits starts at a
+// committed bit P; lane i owns the bits [P + i * S, P + (i + 1) * S) and decodes the tokens that BEGIN there (decode_subseq)
+// into its own slots: lane 0 from P, lane i > 0 first from its own first bit.  In every pass each lane whose entry changed
+// decodes again; then lane i takes the exit bit of lane i - 1 as its entry if that lane ran to its range's end (SUB_NONE).  An
+// entry at or behind the lane's own end leaves the lane empty and is passed on.  After pass k lanes 0 .. k - 1 hold what the
+// serial decode gives, so no entry changes after at most LANES passes.  The lanes up to and including the first whose flag is
+// not SUB_NONE are committed, and P moves to that lane's exit bit.  What needs the output position (a match's distance, the
+// extent's end) is checked when the tokens are committed (token_refused), not here.
+constexpr uint32_t LANES = 64;
+constexpr uint32_t LANE_SLOTS = 48;                   // token slots per lane: the most lane_tokens can be (24 KiB of LDS)
+constexpr uint32_t SUBSEQ_BITS_MAX = 256;
+#ifndef CGAN_PNG_SUBSEQ_BITS
+#define CGAN_PNG_SUBSEQ_BITS 96
+#endif
+#ifndef CGAN_PNG_LANE_TOKENS
+#define CGAN_PNG_LANE_TOKENS 48
+#endif
+constexpr uint32_t SUBSEQ_BITS_DEFAULT = CGAN_PNG_SUBSEQ_BITS, LANE_TOKENS_DEFAULT = CGAN_PNG_LANE_TOKENS;
+// why a lane stopped: its range's end; behind an end-of-block symbol; an invalid symbol or the stream's end; `cap` tokens
+constexpr uint32_t SUB_NONE = 0, SUB_EOB = 1, SUB_BAD = 2, SUB_FULL = 3;
+PNG_HD inline bool lanes_params_ok(int32_t subseq_bits, int32_t lane_tokens) {      // subseq_bits 0: the serial form
+  return subseq_bits >= 0 && subseq_bits <= (int32_t)SUBSEQ_BITS_MAX && subseq_bits % 32 == 0 && lane_tokens >= 1 &&
+         lane_tokens <= (int32_t)LANE_SLOTS;
+}
+PNG_HD inline uint32_t lane_end(uint32_t P, uint32_t lane, uint32_t S) { return P + (lane + 1u) * S; }     // P <= 2^31: no overflow
+PNG_HD inline uint32_t lane_first_entry(uint32_t P, uint32_t lane, uint32_t S) { return P + lane * S; }
+// lane `lane`'s token j of a window's slots: the lanes side by side, so that a wave's lanes write neighbouring words
+PNG_HD inline uint32_t slot_index(uint32_t lane, uint32_t j) { return (j % LANE_SLOTS) * LANES + (lane % LANES); }
+
+struct SubExit {
+  uint32_t bit, flag, count;
+};
+// The tokens that begin in [e, end) of the stream, at most cap <= LANE_SLOTS of them, into slot[slot_index(lane, 0 ..)].  A
+// length symbol, its extra bits, the distance symbol and its extra bits are one token.  -> the exit bit (SUB_NONE, SUB_FULL:
+// where the next token begins; SUB_EOB: behind the end-of-block symbol), the flag and the count.  Writes nothing but the
+// slots, reads nothing outside the stream (Reader::word); every turn consumes a bit or returns.
+PNG_HD inline SubExit decode_subseq(const uint8_t* stream, uint32_t stream_bytes, uint32_t e, const Tables& t, uint32_t end, Token* slot,
+                                    uint32_t lane, uint32_t cap) {
+  Reader r;
+  r.start(stream, stream_bytes);
+  r.seat_bit(e);
+  uint32_t nt = 0;
+  for (;;) {
+    const uint32_t at = (uint32_t)r.used();
+    if (at >= end) return SubExit{at, SUB_NONE, nt};
+    if (nt >= cap) return SubExit{at, SUB_FULL, nt};
+    r.refill();
+    const int sym = decode_symbol(t.lit, r);
+    if (sym < 0 || sym > 285 || r.past_end()) return SubExit{at, SUB_BAD, nt};
+    if (sym < 256) {
+      slot[slot_index(lane, nt++)] = Token{1, (uint8_t)TOK_LITERAL, (uint8_t)sym, 0};
+      continue;
+    }
+    if (sym == 256) return SubExit{(uint32_t)r.used(), SUB_EOB, nt};
+    const uint32_t ls = (uint32_t)sym - 257u;
+    const uint32_t len = length_base(ls) + r.bits(length_extra(ls));
+    r.refill();
+    const int ds = decode_symbol(t.dist, r);
+    if (ds < 0 || ds > 29) return SubExit{at, SUB_BAD, nt};
+    const uint32_t dist = dist_base((uint32_t)ds) + r.bits(dist_extra((uint32_t)ds));
+    if (r.past_end()) return SubExit{at, SUB_BAD, nt};
+    slot[slot_index(lane, nt++)] = Token{(uint16_t)len, (uint8_t)TOK_MATCH, 0, dist};
+  }
+}
+// the commit's checks of a token that goes to byte `at` of an extent of `limit` bytes: at <= limit
+PNG_HD inline bool token_refused(const Token& k, uint32_t at, uint32_t limit) {
+  return (k.kind == TOK_MATCH && k.arg > at) || k.len > limit - at;
+}
+// what the twin reports beside the bytes (cgan_png_inflate_lanes_host)
+constexpr int LANES_STATS = 5;
+constexpr int STAT_WINDOWS = 0, STAT_PASSES = 1, STAT_MAX_PASSES = 2, STAT_FULL_WINDOWS = 3, STAT_TOKENS = 4;
 
 // ---- the unfilter arithmetic -----------------------------------------------------------------------------------------------
 PNG_HD inline uint32_t paeth(uint32_t a, uint32_t b, uint32_t c) {

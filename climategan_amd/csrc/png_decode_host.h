@@ -231,6 +231,91 @@ inline int host_decode(const uint8_t* stream, const cgan_png_desc* desc, uint8_t
   return host_unfilter(d, inflated, s.adler, pixels, status, why, why_len);
 }
 
+// The lane-parallel inflate on the host: inflate_lanes_kernel's rounds with the lanes and the passes taken one
+// after the other -- in every pass first every lane whose entry changed decodes, then every lane looks at its predecessor, as
+// the wave does -- and the commit token by token.  subseq_bits = 0 is the serial form (host_run).  The status is host_decode's:
+// the unfilter runs into a buffer of its own for the Adler-32 and the filter bytes' sake.  *trailer: the stream's Adler-32.
+//   stats[LANES_STATS]: windows, passes in all, the most passes of one window, windows ended by a lane's cap, tokens committed
+inline int host_inflate_lanes(const uint8_t* stream, const cgan_png_desc* desc, int32_t subseq_bits, int32_t lane_tokens, uint8_t* inflated,
+                              uint32_t* trailer, uint32_t* stats, int32_t* status, char* why, size_t why_len) {
+  if (!stream || !desc || !inflated || !trailer || !stats || !status) return snprintf(why, why_len, "null pointer"), -1;
+  if (!desc_ok(*desc)) return snprintf(why, why_len, "not a descriptor the parser produces"), -1;
+  if (!lanes_params_ok(subseq_bits, lane_tokens))
+    return snprintf(why, why_len, "subseq_bits = %d, lane_tokens = %d: 0 or a multiple of 32 up to %u, and 1 .. %u, expected", subseq_bits,
+                    lane_tokens, SUBSEQ_BITS_MAX, LANE_SLOTS), -1;
+  const cgan_png_desc& d = *desc;
+  const uint32_t S = (uint32_t)subseq_bits, cap = (uint32_t)lane_tokens, limit = inflated_bytes(d);
+  *status = CGAN_PNG_OK, *trailer = 0;
+  why[0] = 0;
+  for (int k = 0; k < LANES_STATS; ++k) stats[k] = 0;
+  Inflate s;
+  Tables* t = new Tables;
+  s.start(stream, d.stream_bytes, limit);
+  if (S == 0) {
+    host_run(s, *t, stream, inflated);
+  } else {
+    Token* slot = new Token[LANES * LANE_SLOTS];
+    Token one[1];
+    uint32_t entry[LANES];
+    SubExit ex[LANES];
+    bool changed[LANES];
+    uint32_t pos = 0;
+    auto run = [&](const Token& k) {                     // token_refused said no: pos + len <= limit, arg <= pos
+      for (uint32_t j = 0; j < k.len; ++j, ++pos)
+        inflated[pos] = k.kind == TOK_LITERAL ? k.lit : (k.kind == TOK_MATCH ? inflated[pos - k.arg] : stream[k.arg + j]);
+    };
+    while (s.phase != PHASE_DONE && !s.err) {
+      if (s.phase != PHASE_CODES) {                      // serially: headers, stored blocks, the trailer
+        s.out = pos;
+        if (phase_step(s, *t, one, 0)) run(one[0]);
+        continue;
+      }
+      const uint32_t P = (uint32_t)s.r.used();
+      for (uint32_t i = 0; i < LANES; ++i) entry[i] = lane_first_entry(P, i, S), changed[i] = true;
+      uint32_t passes = 0;
+      for (bool any = true; any && passes < LANES;) {
+        ++passes;
+        for (uint32_t i = 0; i < LANES; ++i)
+          if (changed[i]) {
+            const uint32_t end = lane_end(P, i, S);
+            ex[i] = entry[i] >= end ? SubExit{entry[i], SUB_NONE, 0} : decode_subseq(stream, d.stream_bytes, entry[i], *t, end, slot, i, cap);
+          }
+        any = false, changed[0] = false;
+        for (uint32_t i = LANES - 1; i >= 1; --i) {      // every lane reads its predecessor's exit of this pass
+          changed[i] = ex[i - 1].flag == SUB_NONE && ex[i - 1].bit != entry[i];
+          if (changed[i]) entry[i] = ex[i - 1].bit, any = true;
+        }
+      }
+      uint32_t c = 0;
+      while (c < LANES - 1 && ex[c].flag == SUB_NONE) ++c;
+      stats[STAT_WINDOWS]++, stats[STAT_PASSES] += passes;
+      if (passes > stats[STAT_MAX_PASSES]) stats[STAT_MAX_PASSES] = passes;
+      if (ex[c].flag == SUB_FULL) stats[STAT_FULL_WINDOWS]++;
+      for (uint32_t i = 0; i <= c && !s.err; ++i)
+        for (uint32_t j = 0; j < ex[i].count && !s.err; ++j) {
+          const Token k = slot[slot_index(i, j)];
+          if (token_refused(k, pos, limit)) s.err = CGAN_PNG_CORRUPT;
+          else run(k), stats[STAT_TOKENS]++;
+        }
+      if (ex[c].flag == SUB_BAD) s.err = CGAN_PNG_CORRUPT;
+      if (s.err) break;
+      s.r.seat_bit(ex[c].bit);
+      if (ex[c].flag == SUB_EOB) s.phase = s.last ? PHASE_TRAILER : PHASE_HEADER;
+    }
+    delete[] slot;
+  }
+  delete t;
+  if (s.err) {
+    *status = CGAN_PNG_CORRUPT;
+    return snprintf(why, why_len, "an invalid deflate stream"), 0;
+  }
+  *trailer = s.adler;
+  uint8_t* pixels = new uint8_t[pixel_bytes(d)];
+  const int rc = host_unfilter(d, inflated, s.adler, pixels, status, why, why_len);
+  delete[] pixels;
+  return rc;
+}
+
 // Row-framed files: the row kernel's work row by row -- every row and the tail from its table offset, bounded
 // to its chunk, under the row-end rule -- and, where any of them is refused, the serial decode above, whose verdict stands.
 //   table: rows + 1 offsets for a candidate (cgan_png_row_table_host), not read otherwise.  *path: 0 serial, 1 rows, 2 serial

@@ -791,13 +791,18 @@ PNG_DECODE_MAX_DIM = 8192    # the widest and the highest file cgan_png_decode t
 PNG_OK, PNG_UNSUPPORTED, PNG_CORRUPT = 0, 1, 2      # a file's status bits (climategan_hip.h)
 
 
-def png_decode(blob: torch.Tensor, descs, descs_dev: torch.Tensor):
+def png_decode(blob: torch.Tensor, descs, descs_dev: torch.Tensor, subseq_bits=None, lane_tokens=None):
     """The device PNG decoder.  ``blob``: uint8 device tensor with the files' zlib streams (the IDAT payloads
     as ``cgan_png_stream_host`` joins them); ``descs``: a ctypes array of ``_lib.PngDesc`` as ``cgan_png_parse_host`` filled
     them, ``blob_offset`` (a multiple of 4) / ``out_offset`` set by the caller; ``descs_dev``: the same bytes as a uint8 device
     tensor -> (out, status).  ``out``: one uint8 tensor, file i's [H, W, C] pixels from ``out_offset`` (16-bit grey: two bytes
     a pixel in host order).  ``status``: int32 [N] device tensor, 0 = decoded (PNG_CORRUPT otherwise: the pixels then mean
-    nothing).  Nothing is synchronised."""
+    nothing).  Nothing is synchronised.
+
+    ``subseq_bits`` / ``lane_tokens``: how the inflate spreads a stream over the wave's lanes -- the bits of a
+    lane's subsequence (0: the serial kernel, else a multiple of 32 up to 256) and the most tokens a lane decodes in a window
+    (1 .. 48).  None, the default for both, is ``cgan_png_decode`` with the compiled values (``png.inflate_params``); a given
+    value takes ``cgan_png_decode_lanes``, the other one defaulting to the compiled value.  The results do not depend on them."""
     _need_cuda(blob, descs_dev)
     n = len(descs)
     if blob.dtype != torch.uint8 or descs_dev.dtype != torch.uint8 or not blob.is_contiguous() or not descs_dev.is_contiguous():
@@ -810,9 +815,23 @@ def png_decode(blob: torch.Tensor, descs, descs_dev: torch.Tensor):
     status = _empty((n,), dtype=torch.int32, device=blob.device)
     out = _empty((max(d.out_offset + d.width * d.height * d.channels * (d.bit_depth // 8) for d in descs),), dtype=torch.uint8,
                  device=blob.device)
-    _lib.check(lib.cgan_png_decode(_ptr(blob), blob.numel(), C.addressof(descs), _ptr(descs_dev), n, _ptr(out), out.numel(),
-                                   _ptr(status), _ptr(ws), nbytes, _stream()), "cgan_png_decode")
+    if subseq_bits is None and lane_tokens is None:
+        _lib.check(lib.cgan_png_decode(_ptr(blob), blob.numel(), C.addressof(descs), _ptr(descs_dev), n, _ptr(out), out.numel(),
+                                       _ptr(status), _ptr(ws), nbytes, _stream()), "cgan_png_decode")
+    else:
+        bits, tokens = png_inflate_params()
+        bits, tokens = (bits if subseq_bits is None else int(subseq_bits)), (tokens if lane_tokens is None else int(lane_tokens))
+        _lib.check(lib.cgan_png_decode_lanes(_ptr(blob), blob.numel(), C.addressof(descs), _ptr(descs_dev), n, _ptr(out),
+                                             out.numel(), _ptr(status), _ptr(ws), nbytes, _stream(), bits, tokens),
+                   "cgan_png_decode_lanes")
     return out, status
+
+
+def png_inflate_params():
+    """(subseq_bits, lane_tokens): the compiled values of the lane-parallel inflate."""
+    bits, tokens = C.c_int32(0), C.c_int32(0)
+    _lib.load().cgan_png_inflate_lanes_params(C.addressof(bits), C.addressof(tokens))
+    return bits.value, tokens.value
 
 
 PNG_PATH_SERIAL, PNG_PATH_ROWS, PNG_PATH_REFUSED = 0, 1, 2      # how a file of png_decode_rows was inflated

@@ -3,7 +3,8 @@
 host encoder behind it: a CPU tensor is refused.
 
 The other way: ``probe`` reads a file's chunks on the host, ``decode`` uploads a batch of files' zlib streams
-and inflates and unfilters them on the device (``ops.png_decode``), one wave per file.  Row-framed files (one
+and inflates and unfilters them on the device (``ops.png_decode``), one wave per file with the stream's tokens decoded
+across its 64 lanes (``inflate_params``).  Row-framed files (one
 IDAT chunk per row, as ``encode`` writes them; ``probe`` reports them as ``rows == height``) are inflated one wave per row
 (``ops.png_decode_rows``); ``python -m climategan_amd.repack_png`` turns a folder's PNG files into such files.
 """
@@ -49,6 +50,14 @@ def stream_of(data, d):
     buf = C.create_string_buffer(max(d.stream_bytes, 1))
     _lib.check(_lib.load().cgan_png_stream_host(data, len(data), C.addressof(d), buf, d.stream_bytes), "cgan_png_stream_host")
     return buf.raw[:d.stream_bytes]
+
+
+def inflate_params():
+    """How the device spreads a whole zlib stream over a wave's 64 lanes -> {"subseq_bits": the bits of a lane's
+    subsequence, "lane_tokens": the most tokens a lane decodes in a window}: the compiled values ``decode`` runs with.
+    ``ops.png_decode`` takes other values for a measurement.  Host only."""
+    bits, tokens = ops.png_inflate_params()
+    return {"subseq_bits": bits, "lane_tokens": tokens}
 
 
 def _pixel_bytes(d):

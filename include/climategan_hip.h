@@ -785,6 +785,24 @@ size_t cgan_png_decode_workspace_bytes(const cgan_png_desc* descs_host, int32_t 
 int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host, const cgan_png_desc* descs_dev,
                     int32_t n, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
                     void* stream);
+/* The whole-stream inflate across the wave's 64 lanes.  Inside a block of Huffman codes the wave decodes windows
+ * of 64 * subseq_bits bits: lane i the tokens that begin in its subseq_bits bits, at most lane_tokens of them, first from its
+ * own first bit and again from its predecessor's exit bit until no entry changes; the lanes up to the first that did not
+ * reach its range's end are committed and executed in the stream's order.  Headers, stored blocks and the trailer are serial.
+ * cgan_png_inflate_lanes_params: the compiled defaults, which cgan_png_decode and the whole-stream path of
+ * cgan_png_decode_rows use.
+ * cgan_png_decode_lanes: cgan_png_decode with the two values given.  subseq_bits: 0 (the serial kernel: lane 0 decodes, as
+ * before DESIGN 4.24) or a multiple of 32 up to 256; lane_tokens: 1 .. 48.  Everything else: CGAN_ERR_BAD_ARG, nothing
+ * launched.  The results do not depend on the two values.
+ * cgan_png_inflate_lanes_host (host only): the same rounds lane by lane and pass by pass -> inflated and *status as
+ * cgan_png_decode_host gives them, *trailer: the stream's Adler-32, stats[5]: windows, passes in all, the most passes of one
+ * window, windows that a lane's lane_tokens ended, tokens committed from windows. */
+void cgan_png_inflate_lanes_params(int32_t* subseq_bits, int32_t* lane_tokens);
+int cgan_png_decode_lanes(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host, const cgan_png_desc* descs_dev,
+                          int32_t n, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace, size_t workspace_bytes,
+                          void* stream, int32_t subseq_bits, int32_t lane_tokens);
+int cgan_png_inflate_lanes_host(const uint8_t* stream, const cgan_png_desc* desc, int32_t subseq_bits, int32_t lane_tokens,
+                                uint8_t* inflated, uint32_t* trailer, uint32_t* stats, int32_t* status);
 /* Row-framed files: a file with exactly height + 1 IDAT chunks, the first longer than the zlib header and chunks
  * 1 .. height - 1 not empty, is a candidate, and cgan_png_parse_host sets desc->rows = height for it (0 otherwise).  Such files
  * are what cgan_png_encode_u8 writes: one chunk per row, every row coded on its own and ended by a stored block on the chunk's
