@@ -3,20 +3,17 @@
 // and the Adler sums are png_decode_core.h: the kernels below call them, the host twin (cgan_png_decode_host) runs the same
 // functions serially.
 //
-//   layout_kernel    one thread: every file's place in the workspace (a prefix sum over the files)
+//   layout_kernel    one thread: every file's place in the workspace (a prefix sum over the files); for the row call also
+//                    every candidate's place in the table of row offsets, and the "refused" words zeroed
 //   inflate_kernel   one workgroup of one wave per file: the batch is the parallelism.  Lane 0 decodes up to 64 tokens into
 //                    LDS (decode_tokens; the code tables are in LDS, the bit window in its registers); then the wave executes
-//                    them in the stream's order: a prefix sum over the tokens' lengths gives every token its place, each run
-//                    of literals is scattered at once, each match or stored run is copied by the 64 lanes (a match whose
-//                    distance is shorter than its length as a modular repeat).  The last 32 KiB of output are kept in an LDS
-//                    ring, which is all a match ever reads; the workspace is only written.  Nothing is written to the ring
-//                    ahead of its turn: a byte written early would take the slot of the byte 32 KiB before it, which a match
-//                    still to come may read.  Leaves the stream's Adler-32 trailer.  Since DESIGN 4.24 the serial form:
-//                    cgan_png_decode_lanes with subseq_bits = 0.
+//                    them in the stream's order (execute_tokens).  The last 32 KiB of output are kept in an LDS ring, which
+//                    is all a match ever reads; the workspace is only written.  Leaves the stream's Adler-32 trailer.  Since
+//                    DESIGN 4.24 the serial form: cgan_png_decode_lanes with subseq_bits = 0.
 //   inflate_lanes_kernel  the same workgroup with the decode spread over the 64 lanes: inside a block of codes
 //                    every lane decodes the tokens that begin in its subsequence of a window, first from its own first bit,
 //                    again from its predecessor's exit bit until no entry changes; the committed lanes' tokens go through
-//                    the same execute step 64 at a time.  What cgan_png_decode and cgan_png_decode_rows' fallback launch.
+//                    execute_tokens 64 at a time.  What cgan_png_decode and cgan_png_decode_rows' fallback launch.
 //   unfilter_kernel  one workgroup of UNFILTER_WAVES waves per file, 64 rows per wave at a time as one skewed
 //                    wavefront across the waves: lane r of a wave is at pixel t - r in the wave's step t, its left neighbour
 //                    is its own last result, the two pixels above come from lane r - 1 by __shfl_up; lane 0 reads the row
@@ -26,24 +23,22 @@
 //
 // Row-framed files (cgan_png_decode_rows): files with one IDAT chunk per row, each row coded on its own and ended
 // by a stored block on the chunk's last byte, as this project's encoder writes them (4.17).
-//   layout_rows_kernel   layout_kernel's work, every candidate's place in the table of row offsets, the "refused" words zeroed
 //   inflate_rows_kernel  one workgroup of one wave per (row, file), the tail behind the last row as one more row.  The same
 //                        shape as inflate_kernel -- lane 0 decodes up to 64 tokens (decode_tokens in MODE_ROW: the reader
 //                        bounded to the row's chunk), the wave executes them -- with the row itself as the window, in dynamic
 //                        LDS sized from the batch's longest row.  Whatever a row does not satisfy ORs the file's "refused" word.
 //   inflate_lanes_kernel<true>  the whole-stream kernel for the files that are no candidates or were refused; the others'
 //                        workgroups return.
-// Launches and memsets per call: 1 memset (status) + layout + row inflate + serial inflate + unfilter = 5.  The bounds above
-// hold: a row's reader ends with its chunk, a token's bytes end inside the row, a match starts at or behind the row's first
-// byte, the row buffer's indices are reduced modulo its size, the table's offsets are checked on the host and again by the wave.
+// Launches and memsets per call: 1 memset (status) + layout + row inflate + serial inflate + unfilter = 5.  A row's reader
+// ends with its chunk, and the table's offsets are checked on the host and again by the wave.
 //
-// Bounds: the reader never touches a byte outside [stream, stream + stream_bytes) (Reader::word); decode_tokens hands out a
-// token only if its bytes end inside the file's inflated extent and its source starts at or behind the output's start; a
-// stored run's source is checked against the stream's end.  Loops: a round of inflate_kernel either brings 64 tokens, each of
-// which consumed a bit, or is the last; the copies are bounded by a token's length, the wavefront by the image's size.  In the
-// inflate kernels no wave waits for another: their barriers are __syncthreads() of a one-wave workgroup, reached by all lanes
-// (every branch around them depends on values all lanes share).  The unfilter's waves do wait for each other, at barriers
-// whose number comes from the descriptor alone (see unfilter_kernel).
+// Bounds: the reader never touches a byte outside [stream, stream + stream_bytes) (Reader::word); a stored run's source is
+// checked against the stream's end (block_header); where a token's bytes go and what a match reads: see execute_tokens, the
+// one place that writes inflated bytes.  Loops: a round of the serial kernels either brings 64 tokens, each of which consumed
+// a bit, or is the last; the copies are bounded by a token's length, the wavefront by the image's size.  In the inflate
+// kernels no wave waits for another: their barriers are __syncthreads() of a one-wave workgroup, reached by all lanes (every
+// branch around them depends on values all lanes share).  The unfilter's waves do wait for each other, at barriers whose
+// number comes from the descriptor alone (see unfilter_kernel).
 #include "cgan_common.h"
 #include "png_decode_host.h"
 
@@ -91,26 +86,108 @@ Workspace carve(void* base, const cgan_png_desc* descs, int32_t n, bool rows = f
   return w;
 }
 
-__global__ void layout_kernel(const cgan_png_desc* __restrict__ descs, int n, uint64_t* __restrict__ layout) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  uint64_t at = 0;
-  for (int i = 0; i < n; ++i) {
-    layout[i] = at;
-    at += ((uint64_t)inflated_bytes(descs[i]) + 15) / 16 * 16;
-  }
-}
-
-__global__ void layout_rows_kernel(const cgan_png_desc* __restrict__ descs, int n, Workspace w) {
+// w.table_at and w.refused: the row call's, null otherwise
+__global__ void layout_kernel(const cgan_png_desc* __restrict__ descs, int n, Workspace w) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   uint64_t at = 0;
   uint32_t words = 0;
   for (int i = 0; i < n; ++i) {
     w.layout[i] = at;
     at += ((uint64_t)inflated_bytes(descs[i]) + 15) / 16 * 16;
-    w.table_at[i] = words;
+    if (w.table_at) w.table_at[i] = words;
     words += table_words(descs[i]);
-    w.refused[i] = 0;
+    if (w.refused) w.refused[i] = 0;
   }
+}
+
+// ---- the execute step ------------------------------------------------------------------------------------------------------
+// The window a match reads: the bytes written so far, or the last of them, in LDS.  index(at): where byte `at` of the extent
+// lives, always inside the buffer whatever `at` is.
+struct RingWindow {                           // the last WINDOW bytes of a stream: uint8_t[WINDOW]
+  uint8_t* base;
+  __device__ uint32_t index(uint32_t at) const { return at & (WINDOW - 1); }
+};
+struct RowWindow {                            // a whole row of at most `cap` bytes: uint8_t[cap]
+  uint8_t* base;
+  uint32_t cap;
+  __device__ uint32_t index(uint32_t at) const { return at % cap; }
+};
+
+// Up to 64 tokens, held one per lane (`have`: this lane holds one), appended at byte `pos` of an extent of `limit` bytes that
+// starts at out[0]: a prefix sum over the tokens' lengths gives every token its place, each run of literals is scattered at
+// once, each match or stored run is copied by all 64 lanes (a match whose distance is shorter than its length as a modular
+// repeat), in the stream's order.  All lanes of a one-wave workgroup call it, with the same pos and limit; -> the new pos.
+//   Bounds.  The commit's checks come first, wave-uniformly: a token must end inside the extent and a match must start at or
+// behind out[0] (token_refused).  The tokens from the first refused one on are dropped and *refused is set: the caller ends
+// its file as corrupt (or its row as refused) whatever its decoder's phase says.  decode_tokens has made the same checks for
+// the serial kernels, where the verdict never comes; the lanes' windows are checked here alone.  So every write to `out` lies
+// inside the extent, every index into the window goes through win.index, and a stored run reads stream bytes that
+// block_header checked against the stream's end.
+//   Order.  Nothing is written to the window ahead of its turn: a byte written early into the ring would take the slot of the
+// byte 32 KiB before it, which a match still to come may read.  Hence the literals in front of a match are written, then a
+// barrier, then the match reads and writes, then a barrier; the barriers stand under conditions all lanes share (ballots).
+template <class Window>
+__device__ inline uint32_t execute_tokens(Token k, bool have, uint32_t pos, uint32_t limit, Window win, uint8_t* __restrict__ out,
+                                          const uint8_t* __restrict__ stream, bool* refused) {
+  const uint32_t lane = threadIdx.x;
+  if (!have) k = Token{0, 0, 0, 0};
+  uint32_t incl = k.len;
+  for (int off = 1; off < T; off <<= 1) {
+    const uint32_t v = __shfl_up(incl, off);
+    if ((int)lane >= off) incl += v;
+  }
+  const uint32_t mine = pos + incl - k.len;             // at most 64 * 65535 behind pos <= 2^29: no overflow
+  const unsigned long long no = __ballot(have && (mine > limit || token_refused(k, mine, limit)));
+  *refused = no != 0;
+  if (no) have = have && (int)lane < __ffsll(no) - 1;   // the tokens in front of the first refused one are inside the extent
+  if (!have) k = Token{0, 0, 0, 0};
+  const uint32_t w0 = (uint32_t)k.len | ((uint32_t)k.kind << 16);
+  unsigned long long todo = __ballot(have && k.kind != TOK_LITERAL);
+  int done = -1;                                        // the tokens up to this one are executed
+  while (todo) {                                        // at most 64 turns, the same in every lane
+    const int i = __ffsll(todo) - 1;
+    todo &= todo - 1;
+    if (have && (int)lane > done && (int)lane < i) {    // literals all: the tokens between two set bits
+      win.base[win.index(mine)] = k.lit;
+      out[mine] = k.lit;
+    }
+    __syncthreads();
+    const uint32_t m0 = __shfl(w0, i), arg = __shfl(k.arg, i), q = __shfl(mine, i);
+    const uint32_t len = m0 & 0xFFFFu;
+    if ((m0 >> 16) == TOK_MATCH) {
+      const uint32_t from = q - arg;                    // arg <= q: token_refused
+      for (uint32_t j = lane; j < len; j += T) {
+        const uint8_t v = win.base[win.index(from + (arg < len ? j % arg : j))];
+        win.base[win.index(q + j)] = v;
+        out[q + j] = v;
+      }
+    } else {
+      for (uint32_t j = lane; j < len; j += T) {        // arg + len <= the stream's (the chunk's) end: block_header checked it
+        const uint8_t v = stream[arg + j];
+        win.base[win.index(q + j)] = v;
+        out[q + j] = v;
+      }
+    }
+    __syncthreads();
+    done = i;
+  }
+  if (have && (int)lane > done) {                       // the literals behind the last match
+    win.base[win.index(mine)] = k.lit;
+    out[mine] = k.lit;
+  }
+  const unsigned long long kept = __ballot(have);       // a prefix of the lanes
+  const uint32_t total = kept ? __shfl(incl, 63 - __clzll(kept)) : 0u;
+  __syncthreads();
+  return pos + total;
+}
+
+// The prologue of the whole-stream kernels behind inflate_rows_kernel (cgan_png_decode_rows): writes the file's path -- 1: a
+// candidate that no row refused, 0: not a candidate, 2: refused by the row path -- and -> whether the rows did the file, the
+// same in every lane: the workgroup is done then.
+__device__ inline bool done_by_rows(const cgan_png_desc& d, int file, const uint32_t* __restrict__ refused, int32_t* __restrict__ path) {
+  const bool by_rows = d.rows != 0 && refused[file] == 0;
+  if (threadIdx.x == 0) path[file] = by_rows ? 1 : (d.rows != 0 ? 2 : 0);
+  return by_rows;
 }
 
 // One wave per (row, file): blockIdx.x = the row, or the file's height for the tail; blockIdx.y = the file.
@@ -146,7 +223,8 @@ __global__ __launch_bounds__(T) void inflate_rows_kernel(const uint8_t* __restri
   uint8_t* out = w.inflated + w.layout[file] + (size_t)(tail ? 0u : k) * limit;
   Inflate s;
   s.start_row(stream, begin, end, limit, tail ? MODE_TAIL : MODE_ROW);   // every lane the same; lane 0's is the one that advances
-  uint32_t pos = 0;                                     // bytes executed so far, the same in every lane
+  uint32_t pos = 0;                                     // bytes executed so far, counted from the row's start; the same in every lane
+  bool refused = false;                                 // the execute step's verdict, the same in every lane
   for (;;) {
     if (lane == 0) {
       ctl[0] = decode_tokens(s, tables, tok, BATCH);
@@ -155,59 +233,16 @@ __global__ __launch_bounds__(T) void inflate_rows_kernel(const uint8_t* __restri
     __syncthreads();
     const uint32_t nt = ctl[0] < BATCH ? ctl[0] : BATCH;
     const bool more = ctl[1] != 0 && nt == BATCH;       // a round that is not full is the last one
-    Token q{0, 0, 0, 0};
-    if (lane < nt) q = tok[lane];
-    uint32_t incl = q.len;
-    for (int off = 1; off < T; off <<= 1) {
-      const uint32_t v = __shfl_up(incl, off);
-      if ((int)lane >= off) incl += v;
-    }
-    const uint32_t mine = pos + incl - q.len;           // where my token's bytes go: inside the row (decode_tokens)
-    unsigned long long todo = __ballot(lane < nt && q.kind != TOK_LITERAL);
-    int done = -1;
-    while (todo) {                                      // at most 64 turns, the same in every lane
-      const int i = __ffsll(todo) - 1;
-      todo &= todo - 1;
-      if ((int)lane > done && (int)lane < i) {
-        row[mine % cap] = q.lit;
-        out[mine] = q.lit;
-      }
-      __syncthreads();
-      const Token m = tok[i & (BATCH - 1)];
-      const uint32_t at = __shfl(mine, i);
-      if (m.kind == TOK_MATCH) {
-        const uint32_t from = at - m.arg;               // m.arg <= at: decode_tokens checked it against the row's start
-        for (uint32_t j = lane; j < m.len; j += T) {
-          const uint8_t v = row[(from + (m.arg < m.len ? j % m.arg : j)) % cap];
-          row[(at + j) % cap] = v;
-          out[at + j] = v;
-        }
-      } else {
-        for (uint32_t j = lane; j < m.len; j += T) {    // m.arg + m.len <= the chunk's end: block_header checked it
-          const uint8_t v = stream[m.arg + j];
-          row[(at + j) % cap] = v;
-          out[at + j] = v;
-        }
-      }
-      __syncthreads();
-      done = i;
-    }
-    if ((int)lane > done && lane < nt) {
-      row[mine % cap] = q.lit;
-      out[mine] = q.lit;
-    }
-    pos += __shfl(incl, T - 1);
-    __syncthreads();
-    if (!more) break;
+    pos = execute_tokens(tok[lane], lane < nt, pos, limit, RowWindow{row, cap}, out, stream, &refused);
+    if (!more || refused) break;
   }
   if (lane == 0) {
-    if (s.err || s.phase != PHASE_DONE) atomicOr(&w.refused[file], 1u);
+    if (refused || s.err || s.phase != PHASE_DONE) atomicOr(&w.refused[file], 1u);
     else if (tail) w.adler[file] = s.adler;
   }
 }
 
-// PREDICATED (cgan_png_decode_rows): behind inflate_rows_kernel.  A candidate that no row refused is done (path 1); every other
-// file is decoded here (path 0: not a candidate, 2: refused by the row path).
+// PREDICATED (cgan_png_decode_rows): behind inflate_rows_kernel, for the files the rows did not do (done_by_rows).
 template <bool PREDICATED>
 __global__ __launch_bounds__(T) void inflate_kernel(const uint8_t* __restrict__ blob, const cgan_png_desc* __restrict__ descs,
                                                     Workspace w, int32_t* __restrict__ status, int32_t* __restrict__ path) {
@@ -219,15 +254,15 @@ __global__ __launch_bounds__(T) void inflate_kernel(const uint8_t* __restrict__ 
   const uint32_t lane = threadIdx.x;
   const cgan_png_desc d = descs[file];
   if constexpr (PREDICATED) {
-    const bool by_rows = d.rows != 0 && w.refused[file] == 0;       // the same in every lane
-    if (lane == 0) path[file] = by_rows ? 1 : (d.rows != 0 ? 2 : 0);
-    if (by_rows) return;
+    if (done_by_rows(d, file, w.refused, path)) return;
   }
   const uint8_t* stream = blob + d.blob_offset;
   uint8_t* out = w.inflated + w.layout[file];
+  const uint32_t limit = inflated_bytes(d);
   Inflate s;
-  s.start(stream, d.stream_bytes, inflated_bytes(d));   // every lane the same; lane 0's is the one that advances
+  s.start(stream, d.stream_bytes, limit);               // every lane the same; lane 0's is the one that advances
   uint32_t pos = 0;                                     // bytes executed so far, the same in every lane
+  bool refused = false;                                 // the execute step's verdict, the same in every lane
   for (;;) {
     if (lane == 0) {
       ctl[0] = decode_tokens(s, tables, tok, BATCH);
@@ -236,116 +271,16 @@ __global__ __launch_bounds__(T) void inflate_kernel(const uint8_t* __restrict__ 
     __syncthreads();
     const uint32_t nt = ctl[0] < BATCH ? ctl[0] : BATCH;
     const bool more = ctl[1] != 0 && nt == BATCH;       // a round that is not full is the last one
-    Token k{0, 0, 0, 0};
-    if (lane < nt) k = tok[lane];
-    uint32_t incl = k.len;
-    for (int off = 1; off < T; off <<= 1) {
-      const uint32_t v = __shfl_up(incl, off);
-      if ((int)lane >= off) incl += v;
-    }
-    const uint32_t mine = pos + incl - k.len;           // where my token's bytes go: inside the extent (decode_tokens)
-    // in the stream's order: the literals up to the next match or stored run at once, then that token by all lanes
-    unsigned long long todo = __ballot(lane < nt && k.kind != TOK_LITERAL);
-    int done = -1;                                      // the tokens up to this one are executed
-    while (todo) {                                      // at most 64 turns, the same in every lane
-      const int i = __ffsll(todo) - 1;
-      todo &= todo - 1;
-      if ((int)lane > done && (int)lane < i) {          // literals all: the tokens between two set bits
-        ring[mine & (WINDOW - 1)] = k.lit;
-        out[mine] = k.lit;
-      }
-      __syncthreads();
-      const Token m = tok[i & (BATCH - 1)];
-      const uint32_t q = __shfl(mine, i);
-      if (m.kind == TOK_MATCH) {
-        const uint32_t from = q - m.arg;                // m.arg <= q: decode_tokens checked it
-        for (uint32_t j = lane; j < m.len; j += T) {
-          const uint8_t v = ring[(from + (m.arg < m.len ? j % m.arg : j)) & (WINDOW - 1)];
-          ring[(q + j) & (WINDOW - 1)] = v;
-          out[q + j] = v;
-        }
-      } else {
-        for (uint32_t j = lane; j < m.len; j += T) {    // m.arg + m.len <= stream_bytes: block_header checked it
-          const uint8_t v = stream[m.arg + j];
-          ring[(q + j) & (WINDOW - 1)] = v;
-          out[q + j] = v;
-        }
-      }
-      __syncthreads();
-      done = i;
-    }
-    if ((int)lane > done && lane < nt) {                // the literals behind the last match
-      ring[mine & (WINDOW - 1)] = k.lit;
-      out[mine] = k.lit;
-    }
-    pos += __shfl(incl, T - 1);
-    __syncthreads();
-    if (!more) break;
+    pos = execute_tokens(tok[lane], lane < nt, pos, limit, RingWindow{ring}, out, stream, &refused);
+    if (!more || refused) break;
   }
   if (lane == 0) {
-    if (s.err || s.phase != PHASE_DONE) atomicOr(&status[file], (int32_t)CGAN_PNG_CORRUPT);
+    if (refused || s.err || s.phase != PHASE_DONE) atomicOr(&status[file], (int32_t)CGAN_PNG_CORRUPT);
     w.adler[file] = s.adler;
   }
 }
 
 // ---- the inflate across the wave's lanes ----------------------------------------------------------------------
-// inflate_kernel's execute step on up to 64 tokens held one per lane (`have`: this lane holds one): the commit's checks first,
-// wave-uniformly -- the tokens from the first refused one on are dropped and *refused is set -- then the prefix sum, the runs of
-// literals at once, every match or stored run by all lanes, in the stream's order.  All lanes call it; -> the new `pos`.
-__device__ inline uint32_t execute_tokens(Token k, bool have, uint32_t pos, uint32_t limit, uint8_t* ring, uint8_t* __restrict__ out,
-                                          const uint8_t* __restrict__ stream, bool* refused) {
-  const uint32_t lane = threadIdx.x;
-  if (!have) k = Token{0, 0, 0, 0};
-  uint32_t incl = k.len;
-  for (int off = 1; off < T; off <<= 1) {
-    const uint32_t v = __shfl_up(incl, off);
-    if ((int)lane >= off) incl += v;
-  }
-  const uint32_t mine = pos + incl - k.len;             // at most 64 * 65535 behind pos <= 2^29: no overflow
-  const unsigned long long no = __ballot(have && (mine > limit || token_refused(k, mine, limit)));
-  *refused = no != 0;
-  if (no) have = have && (int)lane < __ffsll(no) - 1;   // the tokens in front of the first refused one are inside the extent
-  if (!have) k = Token{0, 0, 0, 0};
-  const uint32_t w0 = (uint32_t)k.len | ((uint32_t)k.kind << 16);
-  unsigned long long todo = __ballot(have && k.kind != TOK_LITERAL);
-  int done = -1;
-  while (todo) {                                        // at most 64 turns, the same in every lane
-    const int i = __ffsll(todo) - 1;
-    todo &= todo - 1;
-    if (have && (int)lane > done && (int)lane < i) {
-      ring[mine & (WINDOW - 1)] = k.lit;
-      out[mine] = k.lit;
-    }
-    __syncthreads();
-    const uint32_t m0 = __shfl(w0, i), arg = __shfl(k.arg, i), q = __shfl(mine, i);
-    const uint32_t len = m0 & 0xFFFFu;
-    if ((m0 >> 16) == TOK_MATCH) {
-      const uint32_t from = q - arg;                    // arg <= q: token_refused
-      for (uint32_t j = lane; j < len; j += T) {
-        const uint8_t v = ring[(from + (arg < len ? j % arg : j)) & (WINDOW - 1)];
-        ring[(q + j) & (WINDOW - 1)] = v;
-        out[q + j] = v;
-      }
-    } else {
-      for (uint32_t j = lane; j < len; j += T) {        // arg + len <= stream_bytes: block_header checked it
-        const uint8_t v = stream[arg + j];
-        ring[(q + j) & (WINDOW - 1)] = v;
-        out[q + j] = v;
-      }
-    }
-    __syncthreads();
-    done = i;
-  }
-  if (have && (int)lane > done) {                       // the literals behind the last match
-    ring[mine & (WINDOW - 1)] = k.lit;
-    out[mine] = k.lit;
-  }
-  const unsigned long long kept = __ballot(have);       // a prefix of the lanes
-  const uint32_t total = kept ? __shfl(incl, 63 - __clzll(kept)) : 0u;
-  __syncthreads();
-  return pos + total;
-}
-
 // One workgroup of one wave per file, as inflate_kernel.  Lane 0 owns the stream's state (Inflate) and reads block headers,
 // stored blocks and the trailer serially (phase_step); inside a block of codes the wave decodes windows of 64 * S bits by the
 // window rule of png_decode_core.h -- every lane its subsequence into its own LDS slots, again from its predecessor's exit bit
@@ -369,13 +304,12 @@ __global__ __launch_bounds__(T) void inflate_lanes_kernel(const uint8_t* __restr
   const uint32_t lane = threadIdx.x;
   const cgan_png_desc d = descs[file];
   if constexpr (PREDICATED) {
-    const bool by_rows = d.rows != 0 && w.refused[file] == 0;       // the same in every lane
-    if (lane == 0) path[file] = by_rows ? 1 : (d.rows != 0 ? 2 : 0);
-    if (by_rows) return;
+    if (done_by_rows(d, file, w.refused, path)) return;
   }
   const uint8_t* stream = blob + d.blob_offset;
   uint8_t* out = w.inflated + w.layout[file];
   const uint32_t limit = inflated_bytes(d);
+  const RingWindow win{ring};
   if (cap > LANE_SLOTS) cap = LANE_SLOTS;
   Inflate s;
   s.start(stream, d.stream_bytes, limit);               // every lane the same; lane 0's is the one that advances
@@ -396,7 +330,7 @@ __global__ __launch_bounds__(T) void inflate_lanes_kernel(const uint8_t* __restr
     const uint32_t nt = ctl[0] < BATCH ? ctl[0] : BATCH, next = ctl[1];
     uint32_t P = ctl[2];
     bool refused;
-    pos = execute_tokens(tok[lane], lane < nt, pos, limit, ring, out, stream, &refused);      // stored runs: checked by phase_step
+    pos = execute_tokens(tok[lane], lane < nt, pos, limit, win, out, stream, &refused);      // stored runs: checked by phase_step
     corrupt = refused;
     if (next == ENDED || corrupt) break;
     if (next == SERIAL) continue;
@@ -436,7 +370,7 @@ __global__ __launch_bounds__(T) void inflate_lanes_kernel(const uint8_t* __restr
           if (base[l + step] <= g) l += step;
         Token k{0, 0, 0, 0};
         if (have) k = slot[slot_index(l, g - base[l])];
-        pos = execute_tokens(k, have, pos, limit, ring, out, stream, &refused);
+        pos = execute_tokens(k, have, pos, limit, win, out, stream, &refused);
         corrupt = refused;
       }
       __syncthreads();                                  // the slots are read before the next window writes them
@@ -640,69 +574,8 @@ void launch_inflate(int32_t n, hipStream_t s, const uint8_t* blob, const cgan_pn
                        (uint32_t)lane_tokens);
 }
 
-int png_decode_impl(const char* what, const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
-                    const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status, void* workspace,
-                    size_t workspace_bytes, void* stream, int32_t subseq_bits, int32_t lane_tokens) {
-  CGAN_REQUIRE(lanes_params_ok(subseq_bits, lane_tokens),
-               "%s: subseq_bits = %d, lane_tokens = %d: 0 or a multiple of 32 up to %u, and 1 .. %u, expected", what, subseq_bits,
-               lane_tokens, SUBSEQ_BITS_MAX, LANE_SLOTS);
-  CGAN_REQUIRE(blob && descs_dev && out && status && workspace, "%s: null pointer", what);
-  if (const int rc = descs_ok(what, descs_host, n, blob_bytes, true, out_bytes)) return rc;
-  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(blob) % 4 == 0, "%s: the blob is not 4-byte aligned", what);
-  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: the workspace is not 16-byte aligned", what);
-  const Workspace w = carve(workspace, descs_host, n);
-  if (w.bytes > workspace_bytes) {
-    cgan_set_error("%s: the workspace has %zu bytes, %zu are needed", what, workspace_bytes, w.bytes);
-    return CGAN_ERR_WORKSPACE;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)n, s) != hipSuccess) {
-    cgan_set_error("%s: hipMemsetAsync failed", what);
-    return CGAN_ERR_HIP;
-  }
-  hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(64), 0, s, descs_dev, n, w.layout);
-  CGAN_CHECK_LAUNCH("cgan_png_decode (layout)");
-  launch_inflate<false>(n, s, blob, descs_dev, w, status, nullptr, subseq_bits, lane_tokens);
-  CGAN_CHECK_LAUNCH("cgan_png_decode (inflate)");
-  launch_unfilter(n, s, descs_dev, w, out, status);
-  CGAN_CHECK_LAUNCH("cgan_png_decode (unfilter)");
-  return CGAN_OK;
-}
-
-}  // namespace
-
-extern "C" int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
-                               const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status,
-                               void* workspace, size_t workspace_bytes, void* stream) {
-  return png_decode_impl("cgan_png_decode", blob, blob_bytes, descs_host, descs_dev, n, out, out_bytes, status, workspace,
-                         workspace_bytes, stream, (int32_t)SUBSEQ_BITS_DEFAULT, (int32_t)LANE_TOKENS_DEFAULT);
-}
-
-extern "C" int cgan_png_decode_lanes(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
-                                     const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status,
-                                     void* workspace, size_t workspace_bytes, void* stream, int32_t subseq_bits, int32_t lane_tokens) {
-  return png_decode_impl("cgan_png_decode_lanes", blob, blob_bytes, descs_host, descs_dev, n, out, out_bytes, status, workspace,
-                         workspace_bytes, stream, subseq_bits, lane_tokens);
-}
-
-extern "C" void cgan_png_inflate_lanes_params(int32_t* subseq_bits, int32_t* lane_tokens) {
-  if (subseq_bits) *subseq_bits = (int32_t)SUBSEQ_BITS_DEFAULT;
-  if (lane_tokens) *lane_tokens = (int32_t)LANE_TOKENS_DEFAULT;
-}
-
-extern "C" int cgan_png_inflate_lanes_host(const uint8_t* stream, const cgan_png_desc* desc, int32_t subseq_bits, int32_t lane_tokens,
-                                           uint8_t* inflated, uint32_t* trailer, uint32_t* stats, int32_t* status) {
-  char why[200] = "";
-  const int rc = host_inflate_lanes(stream, desc, subseq_bits, lane_tokens, inflated, trailer, stats, status, why, sizeof(why));
-  if (rc || *status) cgan_set_error("cgan_png_inflate_lanes_host: %s", why);
-  return rc ? CGAN_ERR_BAD_ARG : CGAN_OK;
-}
-
-// ---- row-framed files (DESIGN 4.22) ------------------------------------------------------------------------------------
-namespace {
-
-// The host half of cgan_png_decode_rows: the descriptors as cgan_png_decode checks them, and the candidates' tables one file
-// behind the other.  *max_rows / *cap: the grid's width and the row buffer's bytes.
+// The host half of the row path: the descriptors as cgan_png_decode checks them, and the candidates' tables one
+// file behind the other.  *max_rows / *cap: the grid's width and the row buffer's bytes.
 int rows_ok(const char* what, const cgan_png_desc* descs, const uint32_t* tables, size_t table_len, int32_t n, size_t blob_bytes,
             bool with_out, size_t out_bytes, uint32_t* max_rows, uint32_t* cap) {
   if (const int rc = descs_ok(what, descs, n, blob_bytes, with_out, out_bytes)) return rc;
@@ -723,8 +596,86 @@ int rows_ok(const char* what, const cgan_png_desc* descs, const uint32_t* tables
   return CGAN_OK;
 }
 
+// what cgan_png_decode_rows has beyond cgan_png_decode: the candidates' row tables and where every file's path goes
+struct RowPart {
+  const uint32_t *tables_host, *tables_dev;
+  size_t table_len;
+  int32_t* path;
+};
+
+// The one body of cgan_png_decode, cgan_png_decode_lanes and cgan_png_decode_rows (rows: the last one's, else null): the
+// checks, the workspace, the memset and the launches -- with rows the table's checks, the row launch in front of the
+// whole-stream one, and that one predicated.
+int png_decode_impl(const char* what, const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
+                    const cgan_png_desc* descs_dev, const RowPart* rows, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                    void* workspace, size_t workspace_bytes, void* stream, int32_t subseq_bits, int32_t lane_tokens) {
+  CGAN_REQUIRE(lanes_params_ok(subseq_bits, lane_tokens),
+               "%s: subseq_bits = %d, lane_tokens = %d: 0 or a multiple of 32 up to %u, and 1 .. %u, expected", what, subseq_bits,
+               lane_tokens, SUBSEQ_BITS_MAX, LANE_SLOTS);
+  CGAN_REQUIRE(blob && descs_dev && out && status && workspace && (!rows || rows->path), "%s: null pointer", what);
+  uint32_t max_rows = 0, cap = 0;
+  if (const int rc = rows ? rows_ok(what, descs_host, rows->tables_host, rows->table_len, n, blob_bytes, true, out_bytes, &max_rows, &cap)
+                          : descs_ok(what, descs_host, n, blob_bytes, true, out_bytes))
+    return rc;
+  CGAN_REQUIRE(!rows || rows->table_len == 0 || rows->tables_dev, "%s: null pointer", what);
+  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(blob) % 4 == 0, "%s: the blob is not 4-byte aligned", what);
+  CGAN_REQUIRE(!rows || reinterpret_cast<uintptr_t>(rows->tables_dev) % 4 == 0, "%s: the table is not 4-byte aligned", what);
+  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: the workspace is not 16-byte aligned", what);
+  const Workspace w = carve(workspace, descs_host, n, rows != nullptr);
+  if (w.bytes > workspace_bytes) {
+    cgan_set_error("%s: the workspace has %zu bytes, %zu are needed", what, workspace_bytes, w.bytes);
+    return CGAN_ERR_WORKSPACE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)n, s) != hipSuccess) {
+    cgan_set_error("%s: hipMemsetAsync failed", what);
+    return CGAN_ERR_HIP;
+  }
+  hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(64), 0, s, descs_dev, n, w);
+  CGAN_CHECK_LAUNCH(rows ? "cgan_png_decode_rows (layout)" : "cgan_png_decode (layout)");
+  if (max_rows) {
+    hipLaunchKernelGGL(inflate_rows_kernel, dim3(max_rows + 1, n), dim3(T), cap, s, blob, descs_dev, rows->tables_dev,
+                       (uint32_t)rows->table_len, w, cap);
+    CGAN_CHECK_LAUNCH("cgan_png_decode_rows (rows)");
+  }
+  if (rows) launch_inflate<true>(n, s, blob, descs_dev, w, status, rows->path, subseq_bits, lane_tokens);
+  else launch_inflate<false>(n, s, blob, descs_dev, w, status, nullptr, subseq_bits, lane_tokens);
+  CGAN_CHECK_LAUNCH(rows ? "cgan_png_decode_rows (inflate)" : "cgan_png_decode (inflate)");
+  launch_unfilter(n, s, descs_dev, w, out, status);
+  CGAN_CHECK_LAUNCH(rows ? "cgan_png_decode_rows (unfilter)" : "cgan_png_decode (unfilter)");
+  return CGAN_OK;
+}
+
 }  // namespace
 
+extern "C" int cgan_png_decode(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
+                               const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  return png_decode_impl("cgan_png_decode", blob, blob_bytes, descs_host, descs_dev, nullptr, n, out, out_bytes, status, workspace,
+                         workspace_bytes, stream, (int32_t)SUBSEQ_BITS_DEFAULT, (int32_t)LANE_TOKENS_DEFAULT);
+}
+
+extern "C" int cgan_png_decode_lanes(const uint8_t* blob, size_t blob_bytes, const cgan_png_desc* descs_host,
+                                     const cgan_png_desc* descs_dev, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                                     void* workspace, size_t workspace_bytes, void* stream, int32_t subseq_bits, int32_t lane_tokens) {
+  return png_decode_impl("cgan_png_decode_lanes", blob, blob_bytes, descs_host, descs_dev, nullptr, n, out, out_bytes, status,
+                         workspace, workspace_bytes, stream, subseq_bits, lane_tokens);
+}
+
+extern "C" void cgan_png_inflate_lanes_params(int32_t* subseq_bits, int32_t* lane_tokens) {
+  if (subseq_bits) *subseq_bits = (int32_t)SUBSEQ_BITS_DEFAULT;
+  if (lane_tokens) *lane_tokens = (int32_t)LANE_TOKENS_DEFAULT;
+}
+
+extern "C" int cgan_png_inflate_lanes_host(const uint8_t* stream, const cgan_png_desc* desc, int32_t subseq_bits, int32_t lane_tokens,
+                                           uint8_t* inflated, uint32_t* trailer, uint32_t* stats, int32_t* status) {
+  char why[200] = "";
+  const int rc = host_inflate_lanes(stream, desc, subseq_bits, lane_tokens, inflated, trailer, stats, status, why, sizeof(why));
+  if (rc || *status) cgan_set_error("cgan_png_inflate_lanes_host: %s", why);
+  return rc ? CGAN_ERR_BAD_ARG : CGAN_OK;
+}
+
+// ---- row-framed files (DESIGN 4.22) ------------------------------------------------------------------------------------
 extern "C" int cgan_png_row_table_host(const uint8_t* file, size_t file_bytes, const cgan_png_desc* desc, uint32_t* table) {
   char why[160] = "";
   const int rc = host_row_table(file, file_bytes, desc, table, why, sizeof(why));
@@ -752,34 +703,7 @@ extern "C" int cgan_png_decode_rows(const uint8_t* blob, size_t blob_bytes, cons
                                     const cgan_png_desc* descs_dev, const uint32_t* tables_host, const uint32_t* tables_dev,
                                     size_t table_len, int32_t n, uint8_t* out, size_t out_bytes, int32_t* status, int32_t* path,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-  const char* what = "cgan_png_decode_rows";
-  CGAN_REQUIRE(blob && descs_dev && out && status && path && workspace, "%s: null pointer", what);
-  uint32_t max_rows, cap;
-  if (const int rc = rows_ok(what, descs_host, tables_host, table_len, n, blob_bytes, true, out_bytes, &max_rows, &cap)) return rc;
-  CGAN_REQUIRE(table_len == 0 || tables_dev, "%s: null pointer", what);
-  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(blob) % 4 == 0, "%s: the blob is not 4-byte aligned", what);
-  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(tables_dev) % 4 == 0, "%s: the table is not 4-byte aligned", what);
-  CGAN_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: the workspace is not 16-byte aligned", what);
-  const Workspace w = carve(workspace, descs_host, n, true);
-  if (w.bytes > workspace_bytes) {
-    cgan_set_error("%s: the workspace has %zu bytes, %zu are needed", what, workspace_bytes, w.bytes);
-    return CGAN_ERR_WORKSPACE;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)n, s) != hipSuccess) {
-    cgan_set_error("%s: hipMemsetAsync failed", what);
-    return CGAN_ERR_HIP;
-  }
-  hipLaunchKernelGGL(layout_rows_kernel, dim3(1), dim3(64), 0, s, descs_dev, n, w);
-  CGAN_CHECK_LAUNCH("cgan_png_decode_rows (layout)");
-  if (max_rows) {
-    hipLaunchKernelGGL(inflate_rows_kernel, dim3(max_rows + 1, n), dim3(T), cap, s, blob, descs_dev, tables_dev, (uint32_t)table_len, w,
-                       cap);
-    CGAN_CHECK_LAUNCH("cgan_png_decode_rows (rows)");
-  }
-  launch_inflate<true>(n, s, blob, descs_dev, w, status, path, (int32_t)SUBSEQ_BITS_DEFAULT, (int32_t)LANE_TOKENS_DEFAULT);
-  CGAN_CHECK_LAUNCH("cgan_png_decode_rows (inflate)");
-  launch_unfilter(n, s, descs_dev, w, out, status);
-  CGAN_CHECK_LAUNCH("cgan_png_decode_rows (unfilter)");
-  return CGAN_OK;
+  const RowPart rows{tables_host, tables_dev, table_len, path};
+  return png_decode_impl("cgan_png_decode_rows", blob, blob_bytes, descs_host, descs_dev, &rows, n, out, out_bytes, status, workspace,
+                         workspace_bytes, stream, (int32_t)SUBSEQ_BITS_DEFAULT, (int32_t)LANE_TOKENS_DEFAULT);
 }

@@ -34,17 +34,22 @@ inline int host_row_table(const uint8_t* file, size_t file_bytes, const cgan_png
   return 0;
 }
 
+// The token executor: k's bytes to out[at ..] -> the byte behind them.  out[0] is the first byte of the extent (the stream's,
+// the row's); whoever hands the token over has checked at + len <= the extent's bytes and arg <= at (decode_tokens,
+// token_refused) and a stored run against the stream's end (block_header).
+inline uint32_t host_execute(const Token& k, const uint8_t* stream, uint8_t* out, uint32_t at) {
+  for (uint32_t j = 0; j < k.len; ++j, ++at)
+    out[at] = k.kind == TOK_LITERAL ? k.lit : (k.kind == TOK_MATCH ? out[at - k.arg] : stream[k.arg + j]);
+  return at;
+}
+
 // the tokens of one stream, row or tail executed serially: out[0] is the first byte this run of the reader produces
 inline void host_run(Inflate& s, Tables& t, const uint8_t* stream, uint8_t* out) {
   uint32_t at = 0;
   Token tok[64];
   while (s.phase != PHASE_DONE && !s.err) {
     const uint32_t nt = decode_tokens(s, t, tok, 64);
-    for (uint32_t i = 0; i < nt; ++i) {
-      const Token k = tok[i];
-      for (uint32_t j = 0; j < k.len; ++j, ++at)          // at + len <= the limit, arg <= at: decode_tokens checked it
-        out[at] = k.kind == TOK_LITERAL ? k.lit : (k.kind == TOK_MATCH ? out[at - k.arg] : stream[k.arg + j]);
-    }
+    for (uint32_t i = 0; i < nt; ++i) at = host_execute(tok[i], stream, out, at);
   }
 }
 
@@ -260,14 +265,10 @@ inline int host_inflate_lanes(const uint8_t* stream, const cgan_png_desc* desc, 
     SubExit ex[LANES];
     bool changed[LANES];
     uint32_t pos = 0;
-    auto run = [&](const Token& k) {                     // token_refused said no: pos + len <= limit, arg <= pos
-      for (uint32_t j = 0; j < k.len; ++j, ++pos)
-        inflated[pos] = k.kind == TOK_LITERAL ? k.lit : (k.kind == TOK_MATCH ? inflated[pos - k.arg] : stream[k.arg + j]);
-    };
     while (s.phase != PHASE_DONE && !s.err) {
       if (s.phase != PHASE_CODES) {                      // serially: headers, stored blocks, the trailer
         s.out = pos;
-        if (phase_step(s, *t, one, 0)) run(one[0]);
+        if (phase_step(s, *t, one, 0)) pos = host_execute(one[0], stream, inflated, pos);
         continue;
       }
       const uint32_t P = (uint32_t)s.r.used();
@@ -295,7 +296,7 @@ inline int host_inflate_lanes(const uint8_t* stream, const cgan_png_desc* desc, 
         for (uint32_t j = 0; j < ex[i].count && !s.err; ++j) {
           const Token k = slot[slot_index(i, j)];
           if (token_refused(k, pos, limit)) s.err = CGAN_PNG_CORRUPT;
-          else run(k), stats[STAT_TOKENS]++;
+          else pos = host_execute(k, stream, inflated, pos), stats[STAT_TOKENS]++;
         }
       if (ex[c].flag == SUB_BAD) s.err = CGAN_PNG_CORRUPT;
       if (s.err) break;

@@ -791,6 +791,23 @@ PNG_DECODE_MAX_DIM = 8192    # the widest and the highest file cgan_png_decode t
 PNG_OK, PNG_UNSUPPORTED, PNG_CORRUPT = 0, 1, 2      # a file's status bits (climategan_hip.h)
 
 
+def _png_decode_setup(what, blob, descs, descs_dev, workspace_bytes):
+    """What ``png_decode`` and ``png_decode_rows`` share: the tensor checks, then ``workspace_bytes(n)`` (the call's own size
+    query), then the allocations -> (n, nbytes, ws, status, out)."""
+    _need_cuda(blob, descs_dev)
+    n = len(descs)
+    if blob.dtype != torch.uint8 or descs_dev.dtype != torch.uint8 or not blob.is_contiguous() or not descs_dev.is_contiguous():
+        raise RuntimeError("%s: contiguous uint8 tensors expected" % what)
+    if n < 1 or descs_dev.numel() != n * C.sizeof(_lib.PngDesc):
+        raise RuntimeError("%s: %d descriptors on the host, %d bytes of them on the device" % (what, n, descs_dev.numel()))
+    nbytes = workspace_bytes(n)
+    ws = _empty(nbytes, dtype=torch.uint8, device=blob.device)
+    status = _empty((n,), dtype=torch.int32, device=blob.device)
+    out = _empty((max(d.out_offset + d.width * d.height * d.channels * (d.bit_depth // 8) for d in descs),), dtype=torch.uint8,
+                 device=blob.device)
+    return n, nbytes, ws, status, out
+
+
 def png_decode(blob: torch.Tensor, descs, descs_dev: torch.Tensor, subseq_bits=None, lane_tokens=None):
     """The device PNG decoder.  ``blob``: uint8 device tensor with the files' zlib streams (the IDAT payloads
     as ``cgan_png_stream_host`` joins them); ``descs``: a ctypes array of ``_lib.PngDesc`` as ``cgan_png_parse_host`` filled
@@ -803,18 +820,9 @@ def png_decode(blob: torch.Tensor, descs, descs_dev: torch.Tensor, subseq_bits=N
     lane's subsequence (0: the serial kernel, else a multiple of 32 up to 256) and the most tokens a lane decodes in a window
     (1 .. 48).  None, the default for both, is ``cgan_png_decode`` with the compiled values (``png.inflate_params``); a given
     value takes ``cgan_png_decode_lanes``, the other one defaulting to the compiled value.  The results do not depend on them."""
-    _need_cuda(blob, descs_dev)
-    n = len(descs)
-    if blob.dtype != torch.uint8 or descs_dev.dtype != torch.uint8 or not blob.is_contiguous() or not descs_dev.is_contiguous():
-        raise RuntimeError("png_decode: contiguous uint8 tensors expected")
-    if n < 1 or descs_dev.numel() != n * C.sizeof(_lib.PngDesc):
-        raise RuntimeError("png_decode: %d descriptors on the host, %d bytes of them on the device" % (n, descs_dev.numel()))
     lib = _lib.load()
-    nbytes = _size(lib.cgan_png_decode_workspace_bytes(C.addressof(descs), n), "cgan_png_decode_workspace_bytes")
-    ws = _empty(nbytes, dtype=torch.uint8, device=blob.device)
-    status = _empty((n,), dtype=torch.int32, device=blob.device)
-    out = _empty((max(d.out_offset + d.width * d.height * d.channels * (d.bit_depth // 8) for d in descs),), dtype=torch.uint8,
-                 device=blob.device)
+    n, nbytes, ws, status, out = _png_decode_setup("png_decode", blob, descs, descs_dev, lambda n: _size(
+        lib.cgan_png_decode_workspace_bytes(C.addressof(descs), n), "cgan_png_decode_workspace_bytes"))
     if subseq_bits is None and lane_tokens is None:
         _lib.check(lib.cgan_png_decode(_ptr(blob), blob.numel(), C.addressof(descs), _ptr(descs_dev), n, _ptr(out), out.numel(),
                                        _ptr(status), _ptr(ws), nbytes, _stream()), "cgan_png_decode")
@@ -844,26 +852,20 @@ def png_decode_rows(blob: torch.Tensor, descs, descs_dev: torch.Tensor, tables, 
     a candidate is inflated by a wave of its own; a candidate whose rows do not satisfy the row rule and every other file go
     through the serial kernel in the same call.  ``path``: int32 [N] device tensor, PNG_PATH_SERIAL, PNG_PATH_ROWS or
     PNG_PATH_REFUSED (serial after the row path refused).  Nothing is synchronised."""
-    _need_cuda(blob, descs_dev)
-    n = len(descs)
     words = len(tables) if tables is not None else 0
-    if blob.dtype != torch.uint8 or descs_dev.dtype != torch.uint8 or not blob.is_contiguous() or not descs_dev.is_contiguous():
-        raise RuntimeError("png_decode_rows: contiguous uint8 tensors expected")
-    if n < 1 or descs_dev.numel() != n * C.sizeof(_lib.PngDesc):
-        raise RuntimeError("png_decode_rows: %d descriptors on the host, %d bytes of them on the device" % (n, descs_dev.numel()))
-    if words:
-        _need_cuda(tables_dev)
-        if tables_dev.dtype != torch.int32 or not tables_dev.is_contiguous() or tables_dev.numel() != words:
-            raise RuntimeError("png_decode_rows: %d table words on the host, the device's are not the same contiguous int32 words" % words)
-    lib = _lib.load()
     tables_host = C.addressof(tables) if words else None
-    nbytes = _size(lib.cgan_png_decode_rows_workspace_bytes(C.addressof(descs), tables_host, words, n),
-                   "cgan_png_decode_rows_workspace_bytes")
-    ws = _empty(nbytes, dtype=torch.uint8, device=blob.device)
-    status = _empty((n,), dtype=torch.int32, device=blob.device)
+    lib = _lib.load()
+
+    def workspace_bytes(n):
+        if words:
+            _need_cuda(tables_dev)
+            if tables_dev.dtype != torch.int32 or not tables_dev.is_contiguous() or tables_dev.numel() != words:
+                raise RuntimeError("png_decode_rows: %d table words on the host, the device's are not the same contiguous int32 words" % words)
+        return _size(lib.cgan_png_decode_rows_workspace_bytes(C.addressof(descs), tables_host, words, n),
+                     "cgan_png_decode_rows_workspace_bytes")
+
+    n, nbytes, ws, status, out = _png_decode_setup("png_decode_rows", blob, descs, descs_dev, workspace_bytes)
     path = _empty((n,), dtype=torch.int32, device=blob.device)
-    out = _empty((max(d.out_offset + d.width * d.height * d.channels * (d.bit_depth // 8) for d in descs),), dtype=torch.uint8,
-                 device=blob.device)
     _lib.check(lib.cgan_png_decode_rows(_ptr(blob), blob.numel(), C.addressof(descs), _ptr(descs_dev), tables_host,
                                         _ptr(tables_dev) if words else None, words, n, _ptr(out), out.numel(), _ptr(status),
                                         _ptr(path), _ptr(ws), nbytes, _stream()), "cgan_png_decode_rows")

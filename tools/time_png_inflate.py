@@ -6,6 +6,7 @@ inflate in its forms, on the same files:
   serial0     the same with ``subseq_bits=0``: this build's serial kernel, lane 0 decodes
   parent      the same bytes through ``cgan_png_decode`` of ANOTHER build of the library loaded beside this one
               (``--serial-lib``: the parent commit's libcgan_hip.so, the yardstick); left out without it
+  parent_serial0  the other build's ``cgan_png_decode_lanes`` with ``subseq_bits=0``: the yardstick of ``serial0``
   host_pool   ``PIL.Image.open`` + ``np.asarray`` from a 16-thread pool, each array uploaded
 
 usage: python tools/time_png_inflate.py [--serial-lib PATH] [--reps 9] [--warmup 2] [--json profiles/png_inflate_lanes.json]
@@ -119,9 +120,12 @@ def main():
         parent_lib.cgan_png_decode_workspace_bytes.restype, parent_lib.cgan_png_decode_workspace_bytes.argtypes = C.c_size_t, [P, C.c_int32]
         parent_lib.cgan_png_decode.restype = C.c_int
         parent_lib.cgan_png_decode.argtypes = [P, C.c_size_t, P, P, C.c_int32, P, C.c_size_t, P, P, C.c_size_t, P]
+        parent_lib.cgan_png_decode_lanes.restype = C.c_int
+        parent_lib.cgan_png_decode_lanes.argtypes = parent_lib.cgan_png_decode.argtypes + [C.c_int32, C.c_int32]
 
-    def parent(files):
-        """``ours`` with the batch handed to the other library's ``cgan_png_decode``: the same probe, uploads and wait."""
+    def parent(files, serial0=False):
+        """``ours`` with the batch handed to the other library's ``cgan_png_decode`` (serial0: its ``cgan_png_decode_lanes`` with
+        ``subseq_bits=0``, its serial kernel): the same probe, uploads and wait."""
         taken = [png.probe(f)[0] for f in files]
         blob, descs, descs_dev = png.upload(list(zip(taken, files)), "cuda")
         n = len(descs)
@@ -130,8 +134,12 @@ def main():
         ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
         status = torch.empty(n, dtype=torch.int32, device="cuda")
         out = torch.empty(max(d.out_offset + d.width * d.height * d.channels for d in descs), dtype=torch.uint8, device="cuda")
-        rc = parent_lib.cgan_png_decode(blob.data_ptr(), blob.numel(), C.addressof(descs), descs_dev.data_ptr(), n, out.data_ptr(),
-                                        out.numel(), status.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
+        call_args = (blob.data_ptr(), blob.numel(), C.addressof(descs), descs_dev.data_ptr(), n, out.data_ptr(), out.numel(),
+                     status.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
+        if serial0:
+            rc = parent_lib.cgan_png_decode_lanes(*call_args, 0, png.inflate_params()["lane_tokens"])
+        else:
+            rc = parent_lib.cgan_png_decode(*call_args)
         assert rc == 0 and status.tolist() == [0] * n                                     # the one wait
         return [png.image_view(out, d) for d in descs]
 
@@ -152,9 +160,10 @@ def main():
                 runs = {"lanes": lambda: result.__setitem__("lanes", ours(files)),
                         "serial0": lambda: result.__setitem__("serial0", ours(files, subseq_bits=0)),
                         "parent": lambda: result.__setitem__("parent", parent(files)),
+                        "parent_serial0": lambda: result.__setitem__("parent_serial0", parent(files, serial0=True)),
                         "host_pool": lambda: result.__setitem__("host_pool", list(pool.map(read, files)))}
                 if parent_lib is None:
-                    del runs["parent"]
+                    del runs["parent"], runs["parent_serial0"]
                 if args.also:
                     bits, tokens = (int(v) for v in args.also.split(","))
                     runs["lanes_%d_%d" % (bits, tokens)] = lambda: result.__setitem__("also", ours(files, subseq_bits=bits, lane_tokens=tokens))

@@ -26,7 +26,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tools"))
 
 CASES = ((640, 640, 1), (640, 640, 16), (640, 640, 128), (1200, 1800, 1), (1200, 1800, 16))
-KERNELS = ("layout_rows_kernel", "inflate_rows_kernel", "inflate_kernel", "unfilter_kernel")
+KERNELS = ("layout_kernel", "inflate_rows_kernel", "inflate_kernel", "unfilter_kernel")
 DISTINCT = 8
 
 
